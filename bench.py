@@ -15,7 +15,11 @@ synchronize on both sides, max over ranks (RCCL all-reduce of one float).
 cpu_baseline: the oracle (oracle/liboracle.so, single thread, kind "port") on a bounded sample of the
 same workload (the config-2 generator with fewer pods), rank 0 at N=1 only.
 
-Extra legs on the same line (the headline `value` is config 2):
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the headline line; its
+nodeclaims / pods_placed fields are read from the last timed step's result. --dump-outputs DIR also writes that result
+(what the caller of the last timed kp_solve received) as DIR/<name>.npy, float64: see _dump_outputs.
+
+--full adds the cpu_baseline above and these legs to the same line (the headline `value` is config 2):
   feasibility   CompatibleAvailableFilter rows x instance types (HBM roofline)
   configs       config 1 (1k pods, kwok pool), config 3 (100k pods, zone + hostname topology spread onto 5k
                 existing nodes), config 5 (1M-pod burst, 20 weighted pools with limits, GPU/Neuron pools)
@@ -56,8 +60,17 @@ def main():
     ap.add_argument("--c3-pods", type=int, default=100_000)
     ap.add_argument("--c5-pods", type=int, default=1_000_000)
     ap.add_argument("--feas-rows", type=int, default=50_000)
-    ap.add_argument("--quick", action="store_true", help="config 2 + feasibility only (profiling runs)")
+    ap.add_argument("--quick", action="store_true", help="with --full: config 2 + feasibility only (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the CPU baselines and the extra legs (feasibility, configs "
+                         "1/3/5, consolidation); the options above other than --pods only matter with it")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's result (placement, NodeClaims) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if (args.quick or args.only_general) and not args.full:
+        ap.error("--quick and --only-general select legs of the --full run: pass --full with them")
     t_start = time.perf_counter()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -117,11 +130,16 @@ def main():
         _solve_step(sched, kcomm)
     barrier()
     t0 = time.perf_counter()
-    runs = [_solve_step(sched, kcomm)["stats"] for _ in range(args.steps)]
+    runs = [_solve_step(sched, kcomm)["stats"] for _ in range(args.steps - 1)]
+    last_stats, read_last, release_last = _solve_step_keep(sched, kcomm)  # the last timed step: its result is kept
+    runs.append(last_stats)
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
 
-    res = _solve_step(sched, kcomm, read=True)  # one more Solve for result sanity (not timed)
+    res = read_last()  # what the last timed step returned, copied into Python outside the timed region
+    release_last()
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, res)
     placed = int((res["placement"] != -1).sum())
     mean = lambda k: sum(r[k] for r in runs) / len(runs)
     k_ms, f_ms, dev_ms = mean("solve_kernel_ms"), mean("finalize_kernel_ms"), mean("device_ms")
@@ -176,7 +194,7 @@ def main():
             "latency": _latency_roofline(k_ms, prob.n_pods),
         },
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = _cpu_baseline(cat, args.cpu_sample_pods)
         _attach_full_size(line["cpu_baseline"], "config2")
     def progress(msg):  # stderr progress per leg (rank 0): long runs keep writing
@@ -184,9 +202,10 @@ def main():
             print(f"[bench] {msg} ({time.perf_counter() - t_start:.1f} s)", file=sys.stderr, flush=True)
 
     progress(f"config2 solve done: {value:.0f} pods/s")
-    line["feasibility"] = _feasibility(args, cat, ctx, prob, barrier, max_over_ranks, world)
-    progress("feasibility done")
-    if not args.quick:
+    if args.full:
+        line["feasibility"] = _feasibility(args, cat, ctx, prob, barrier, max_over_ranks, world)
+        progress("feasibility done")
+    if args.full and not args.quick:
         cfgs = {}
         # config 2 with ReplicaSet bursts (each deployment's pods created within 2 s): 109-pod same-level runs
         cfgs["config2_burst"] = _solve_leg("config2_burst", synth.config2(cat, n_pods=args.pods, seed=2, burst=True), ctx,
@@ -205,7 +224,7 @@ def main():
                                      max_over_ranks, world, 1, 0, kcomm,
                                      None if (rank or world > 1 or args.no_cpu_baseline) else ("5", 6000))
         line["configs"] = cfgs
-    if not args.no_consolidation and not args.quick:
+    if args.full and not args.no_consolidation and not args.quick:
         progress("config5 done")
         line["consolidation"] = _consolidation(args, cat, ctx, dist, rank, world, barrier, kcomm)
         progress("consolidation done")
@@ -230,6 +249,76 @@ def _solve_step(sched, kcomm, read=False):
         return plan.run(read=read)
     finally:
         plan.close()
+
+
+def _solve_step_keep(sched, kcomm):
+    """_solve_step(read=False) with the same C-ABI calls, except that the kp_solve_result (and with N ranks its plan)
+    outlives the step: returns (stats, read, release). read() copies the result into Python (kpamd.read_result),
+    release() destroys it; both are the caller's to run after the timed region."""
+    import ctypes as C
+    import kpamd
+    from kpamd import abi
+    lib = sched.ctx.lib
+    res = C.c_void_p()
+    plan = None
+    if kcomm is None:
+        si = sched.solve_in()
+        kpamd._check(lib, lib.kp_solve(sched.ctx.h, C.byref(si), C.byref(res)))
+    else:
+        plan = sched.prepare(kcomm)
+        try:
+            kpamd._check(lib, lib.kp_solve_run(plan.h, C.byref(res)))
+        except Exception:
+            plan.close()
+            raise
+    st = abi.SolveStats()
+    lib.kp_result_stats(res, C.byref(st))
+
+    def release():
+        lib.kp_result_destroy(res)
+        if plan is not None:
+            plan.close()
+
+    return kpamd.stats_dict(st), lambda: kpamd.read_result(lib, res, sched.problem.n_pods), release
+
+
+def _dump_outputs(out_dir, res):
+    """--dump-outputs: one Solve result (kpamd.read_result: the placement and the NodeClaims the caller of kp_solve
+    receives) as float64 .npy files, every value an integer that float64 holds exactly (well under 1 MB at 50k pods):
+      placement                     [pods]       NodeClaim index, -1 unschedulable, <= -2 an existing node
+      nodeclaim_nodepool            [claims]     NodePool index
+      nodeclaim_n_remaining         [claims]     instance-type options left
+      nodeclaim_pod_offsets / _pods              CSR: the claim's pods in the order they were added
+      nodeclaim_option_offsets / _options        CSR: the claim's remaining instance-type options in result order
+      nodeclaim_requests            [claims, resources]  milli-units in kp_abi resource order, -1 = not present
+      nodeclaim_requirements_crc32  [claims]     CRC-32 of the claim's requirements (key, operator, values, minValues)
+                                                 in result order: text has no array form, equal results give equal sums"""
+    import zlib
+    import numpy as np
+    from kpamd import abi
+    ncs = res["nodeclaims"]
+    f64 = lambda x, shape=None: np.asarray(x, dtype=np.float64).reshape(shape if shape is not None else -1)
+
+    def csr(key):
+        offs = np.zeros(len(ncs) + 1, dtype=np.float64)
+        offs[1:] = np.cumsum([len(n[key]) for n in ncs])
+        return offs, f64([v for n in ncs for v in n[key]])
+
+    pod_offs, pods = csr("pods")
+    opt_offs, opts = csr("options")
+    out = {
+        "placement": f64(res["placement"]),
+        "nodeclaim_nodepool": f64([n["nodepool"] for n in ncs]),
+        "nodeclaim_n_remaining": f64([n["n_remaining"] for n in ncs]),
+        "nodeclaim_pod_offsets": pod_offs, "nodeclaim_pods": pods,
+        "nodeclaim_option_offsets": opt_offs, "nodeclaim_options": opts,
+        "nodeclaim_requests": f64([[n["requests"].get(r, -1) for r in abi.RES_NAMES] for n in ncs],
+                                  (len(ncs), len(abi.RES_NAMES))),
+        "nodeclaim_requirements_crc32": f64([zlib.crc32(json.dumps(n["requirements"]).encode()) for n in ncs]),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def _solve_leg(name, prob, ctx, barrier, max_over_ranks, world, steps, warmup, kcomm, cpu):

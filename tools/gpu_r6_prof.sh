@@ -1,13 +1,13 @@
 #!/bin/bash
 # GPU call: the full bench line, then per-leg rocprofv3 passes (tools/prof_leg.py): kernel-trace stats, FETCH_SIZE and
 # WRITE_SIZE (separate runs), SQ instruction-mix counters for the consolidation legs; tools/pmc_traffic.py keys the
-# traffic by leg. Output under gpurun_out/r6prof/. SKIP_BENCH=1 skips the bench; LEGS overrides the leg list.
+# traffic by leg. Output under $OUT/r6prof/. SKIP_BENCH=1 skips the bench; LEGS overrides the leg list.
 set -o pipefail
-cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out/r6prof
+cd "$(dirname "$0")/.."; OUT=${OUT:-bench_out}; mkdir -p $OUT/r6prof
 export TMPDIR=/tmp
-O=gpurun_out/r6prof
+O=$OUT/r6prof
 if [ -z "$SKIP_BENCH" ]; then
-  timeout -k 10 600 python -u bench.py > $O/bench.json 2> $O/bench.err || { echo "bench rc=$?"; tail -30 $O/bench.err; exit 1; }
+  timeout -k 10 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { echo "bench rc=$?"; tail -30 $O/bench.err; exit 1; }
   cat $O/bench.json
 fi
 LEGS=${LEGS:-"solve2 feas_rows feas_compact sweep general"}
