@@ -21,6 +21,9 @@
  *                             pkg/controllers/provisioning/scheduling/scheduler.go), reached from
  *                             R:pkg/providers/instancetype/suite_test.go:93,279 (NewProvisioner/ExpectProvisioned),
  *                             followed by Results.TruncateInstanceTypes(MaxInstanceTypes).
+ *   kp_cluster_simulate / kp_consolidate_argmin <- upstream disruption computeConsolidation over candidate subsets
+ *                             (R:website/content/en/preview/concepts/disruption.md:89-128); the _budgeted forms also
+ *                             apply the NodePools' disruption budgets (disruption.md:274-333) per subset on the device.
  *
  * Conventions
  *   - Every function returns int32: KP_OK (0) or a negative KP_E_* code. kp_last_error() gives text.
@@ -875,6 +878,30 @@ int32_t kp_consolidate_argmin_cancellable(kp_cluster_plan* plan, kp_comm* comm, 
                                           const uint32_t* offsets, const uint32_t* nodes, uint32_t n_subsets,
                                           uint64_t base_index, int32_t multi_node, kp_sim_result* out, kp_choice* best,
                                           kp_solve_stats* stats);
+/* NodePool disruption budgets (spec.disruption.budgets; R:website/content/en/preview/concepts/disruption.md:274-333,
+ * R:pkg/apis/crds/karpenter.sh_nodepools.yaml:95-135), additive to ABI v12. allowed[p] is the caller's allowed
+ * disruptions of cluster->nodepools[p] for the reason it asks with (Underutilized for consolidation):
+ *   max(0, min over the active budgets listing the reason or none of value(budget, total) - deleting - not_ready),
+ * KP_BUDGET_UNLIMITED where no budget applies. A subset is admissible iff, for every NodePool, the number of its
+ * members owned by that pool (the node's karpenter.sh/nodepool label) is <= allowed[pool]; this is upstream's candidate
+ * walk generalised to arbitrary subsets, decided on the device where the subsets are (budget_gate_kernel, before the
+ * simulations). A blocked subset is not simulated: its out entry is all zero (KP_DECISION_NOOP), it counts in
+ * kp_choice.counts[0] and in *n_blocked, and it can never be the best. With a communicator *n_blocked is the calling
+ * rank's own count only (the ranks' records carry no such field). allowed == NULL: exactly the cancellable call.
+ * Errors: KP_E_INVAL when n_allowed differs from the cluster's NodePool count, or when a subset names a node whose
+ * karpenter.sh/nodepool label is missing or names no NodePool of the cluster (the message names subset and node);
+ * KP_E_UNSUPPORTED for more than 256 NodePools (the Go path then runs). Cancellation, stale-plan refusal and the
+ * collective's "no peer is left waiting" rule hold as for the cancellable calls; a failure of the gate is a
+ * KP_CHOICE_FAILED record. stats (general path): phase_cycles[0] + phase_cycles[1] count the admissible subsets only. */
+#define KP_BUDGET_UNLIMITED 0xFFFFFFFFu
+int32_t kp_cluster_simulate_budgeted(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets,
+                                     const uint32_t* nodes, uint32_t n_subsets, int32_t multi_node,
+                                     const uint32_t* allowed, uint32_t n_allowed, kp_sim_result* out, uint64_t* n_blocked,
+                                     kp_solve_stats* stats);
+int32_t kp_consolidate_argmin_budgeted(kp_cluster_plan* plan, kp_comm* comm, kp_cancel* cancel, const uint32_t* offsets,
+                                       const uint32_t* nodes, uint32_t n_subsets, uint64_t base_index, int32_t multi_node,
+                                       const uint32_t* allowed, uint32_t n_allowed, kp_sim_result* out, kp_choice* best,
+                                       uint64_t* n_blocked, kp_solve_stats* stats);
 /* The reduction kp_consolidate_argmin applies to the gathered per-rank records (host-only; exposed for callers that
  * reduce over another transport, and for tests): counts are summed, the best record wins. */
 int32_t kp_choice_reduce(const kp_choice* per_rank, uint32_t n, kp_choice* out);

@@ -418,6 +418,38 @@ struct SimArgs {
   const int32_t* cancel;             // kp_cancel flag (host-mapped) or null: polled between a wave's subsets
 };
 
+// sim_kernel's second argument: SimAll walks every subset of the batch, SimLive (the budget-gated instantiation) the
+// admissible ones, ascending
+struct SimAll {
+  static constexpr bool gated = false;
+  static constexpr const uint32_t* live = nullptr;
+};
+struct SimLive {
+  static constexpr bool gated = true;
+  const uint32_t* live;
+};
+// budget gate over the resident CSR batch (budget_gate_kernel, gate_scan_kernel, gate_scatter_kernel)
+#define GATE_WAVES 4
+#define GATE_PER_WAVE 16
+#define GATE_BLOCK (GATE_WAVES * GATE_PER_WAVE)  // subsets per block, contiguous
+#define GATE_MAX_POOLS 256
+struct GateArgs {
+  int32_t n_subsets;
+  int32_t n_pools;                   // <= GATE_MAX_POOLS
+  int32_t n_nodes;                   // N
+  const uint32_t* sub_off;           // [n_subsets + 1]
+  const uint32_t* sub_nodes;
+  const uint16_t* node_pool;         // [N], every member's entry < n_pools (checked on the host)
+  const uint32_t* allowed;           // [n_pools] KP_BUDGET_UNLIMITED: no limit
+  uint8_t* gate;                     // [n_subsets] 1 admissible, 0 blocked
+  SimOut* out;                       // blocked subsets: the zero no-op
+  uint32_t* blk_cnt;                 // [n_blocks] admissible subsets of the block
+  uint32_t* blk_off;                 // [n_blocks] exclusive scan of blk_cnt
+  uint32_t* live;                    // [n_subsets] ascending admissible subset indices
+  uint32_t* n_live;                  // [1]
+};
+hipError_t launch_budget_gate(const GateArgs& g, hipStream_t s);
+
 // kp_consolidate_argmin: per-block partial bests, and the record each rank contributes to the all-gather
 struct ArgmaxPart {
   double savings;
@@ -434,7 +466,9 @@ hipError_t launch_argmax(const SimOut* out, int n, ArgmaxPart* part, int n_parts
 
 hipError_t launch_sim_prep(const SimArgs& a, hipStream_t s);
 hipError_t launch_sim(const SimArgs& a, int blocks, size_t dyn_lds, hipStream_t s);
-const void* sim_kernel_ptr();
+// the gated instantiation (disruption budgets): the waves walk live[0 .. n_live), the admissible subsets, ascending
+hipError_t launch_sim_gated(const SimArgs& a, const uint32_t* live, int n_live, int blocks, size_t dyn_lds, hipStream_t s);
+const void* sim_kernel_ptr(bool gated = false);
 #define SIM_WAVES 4
 
 hipError_t launch_solve(const SolveArgs& a, int nw, size_t dyn_lds, hipStream_t s);

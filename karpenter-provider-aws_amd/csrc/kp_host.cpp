@@ -4777,6 +4777,17 @@ struct kp_cluster_plan {
   };
   vector<NodeOffer> node_offer;
   vector<uint8_t> node_flags;
+  // disruption budgets: the NodePool each node's karpenter.sh/nodepool label names (0xFFFF: none), derived at prepare
+  vector<uint16_t> node_pool;
+  const uint16_t* d_node_pool = nullptr;  // its resident copy (batched path)
+  uint32_t n_pools = 0;
+};
+
+// kp_*_budgeted: the caller's allowed[] and the count of subsets it blocked
+struct BudgetGate {
+  const uint32_t* allowed;
+  uint32_t n_allowed;
+  uint64_t blocked = 0;
 };
 
 namespace {
@@ -4808,6 +4819,31 @@ bool NodeCandidatePrice(const HostType& t, const std::map<string, string>& label
   }
   *price = p;
   return any;
+}
+
+// The per-node NodePool table of a cluster plan (disruption budgets count a subset's members per owning NodePool)
+void FillNodePools(const kp_cluster* cl, kp_cluster_plan* plan) {
+  std::unordered_map<string, uint32_t> idx;
+  for (uint32_t i = 0; i < cl->n_nodepools; i++) idx.emplace(cl->nodepools[i].name ? cl->nodepools[i].name : "", i);
+  plan->n_pools = cl->n_nodepools;
+  plan->node_pool.assign(std::max<uint32_t>(cl->n_nodes, 1), 0xFFFF);
+  for (uint32_t i = 0; i < cl->n_nodes; i++) {
+    const kp_existing_node& n = cl->nodes[i].node;
+    for (uint32_t j = 0; j < n.n_labels; j++) {
+      if (!n.labels[j].key || Normalize(n.labels[j].key) != kNodePool) continue;
+      auto f = idx.find(n.labels[j].value ? n.labels[j].value : "");
+      if (f != idx.end() && f->second < 0xFFFF) plan->node_pool[i] = (uint16_t)f->second;
+    }
+  }
+}
+// Budget arguments against the plan (kp_*_budgeted)
+int32_t CheckBudget(const kp_cluster_plan* plan, const BudgetGate* bg) {
+  if (!bg->allowed) return fail(KP_E_INVAL, "null allowed");
+  if (bg->n_allowed != plan->n_pools)
+    return fail(KP_E_INVAL, "n_allowed %u, the cluster has %u NodePools", bg->n_allowed, plan->n_pools);
+  if (plan->n_pools > GATE_MAX_POOLS)
+    return fail(KP_E_UNSUPPORTED, "disruption budgets over %u NodePools (max %d)", plan->n_pools, GATE_MAX_POOLS);
+  return KP_OK;
 }
 }  // namespace
 
@@ -4843,6 +4879,7 @@ static int32_t PrepareGeneral(kp_ctx* ctx, const kp_cluster* cl, kp_cluster_plan
   auto plan = std::make_unique<kp_cluster_plan>();
   plan->ctx = ctx;
   plan->N = (int)cl->n_nodes;
+  FillNodePools(cl, plan.get());
   plan->general = std::make_unique<OwnedCluster>(cl);
   pt.lap("general: owned copy");
   // the superset Solve of the batched simulations, built now (it validates every node and pod as well); a cluster
@@ -4902,6 +4939,7 @@ int32_t kp_cluster_prepare(kp_ctx* ctx, const kp_cluster* cl, kp_cluster_plan** 
   Compiled& C = *plan->cp;
   const int N = (int)cl->n_nodes;
   plan->N = N;
+  FillNodePools(cl, plan.get());
   vector<kp_existing_node> ex(N);
   for (int i = 0; i < N; i++) ex[i] = cl->nodes[i].node;
   kp_solve_in in;
@@ -5082,6 +5120,7 @@ int32_t kp_cluster_prepare(kp_ctx* ctx, const kp_cluster* cl, kp_cluster_plan** 
   const size_t o_tlp = blob.put(C.tmpl_limit_present);
   const size_t o_trem = blob.put(C.tmpl_remaining);
   const size_t o_shpc = blob.put(C.shape_hp_conf), o_shpa = blob.put(C.shape_hp_add), o_exhp = blob.put(C.ex_hp);
+  const size_t o_npool = blob.put(plan->node_pool);
   const size_t host_bytes = blob.host.size();
   const size_t o_usable = blob.reserve(sizeof(uint64_t) * (size_t)std::max(SL, 1) * std::max(EW, 1));
   const size_t o_tres = blob.reserve(sizeof(SimNC) * (size_t)std::max(SL, 1));
@@ -5146,6 +5185,7 @@ int32_t kp_cluster_prepare(kp_ctx* ctx, const kp_cluster* cl, kp_cluster_plan** 
   a.node_flags = base + o_nflags;
   a.node_name = (const uint32_t*)(base + o_nname);
   a.type_name = (const uint32_t*)(base + o_tname);
+  plan->d_node_pool = (const uint16_t*)(base + o_npool);
   a.ct_key = ctk;
   a.spot_bit = ctk >= 0 ? d.bit(ctk, "spot") : -1;
   a.od_bit = ctk >= 0 ? d.bit(ctk, "on-demand") : -1;
@@ -6265,7 +6305,7 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
 }
 
 static int32_t GeneralSimLocked(kp_cluster_plan* plan, const uint32_t* offsets, const uint32_t* nodes,
-                                uint32_t n_subsets, int32_t multi_node, SimArgs& a, kp_cancel* cancel) {
+                                uint32_t n_subsets, int32_t multi_node, SimArgs& a, kp_cancel* cancel, BudgetGate* bg) {
   kp_ctx* ctx = plan->ctx;
   const kp_cluster& cl = plan->general->cl;
   const int N = (int)cl.n_nodes;
@@ -6325,6 +6365,11 @@ static int32_t GeneralSimLocked(kp_cluster_plan* plan, const uint32_t* offsets, 
       mark[c] = 1;
     }
   }
+  if (bg)  // disruption budgets: every member must be owned by a NodePool of the cluster
+    for (uint32_t s = 0; s < n_subsets; s++)
+      for (uint32_t k = offsets[s]; k < offsets[s + 1]; k++)
+        if (plan->node_pool[nodes[k]] == 0xFFFF)
+          return fail(KP_E_INVAL, "subset %u: node %u has no NodePool of the cluster (karpenter.sh/nodepool)", s, nodes[k]);
   // the batched path: built once per plan (again after an offering refresh of its catalogues)
   if (plan->gb) {
     const SolveBase& B = *plan->gb->C->B;
@@ -6348,9 +6393,16 @@ static int32_t GeneralSimLocked(kp_cluster_plan* plan, const uint32_t* offsets, 
   memset(plan->general_phase, 0, sizeof plan->general_phase);
   double dev_ms = 0, host_ms[2] = {0, 0};  // the batch's host work: overlays + arguments, decisions
   vector<int> batched, single;
-  vector<char> batchable(n_subsets, 0);
+  vector<char> batchable(n_subsets, 0), blocked(n_subsets, 0);
   ParallelFor((int)n_subsets, [&](int s_lo, int s_hi, int) {
+    vector<uint32_t> per_pool(bg ? plan->n_pools : 0);
     for (int s = s_lo; s < s_hi; s++) {
+      if (bg) {  // the budget gate's rule (budget_gate_kernel): no NodePool owns more members than it allows
+        std::fill(per_pool.begin(), per_pool.end(), 0u);
+        for (uint32_t c : cands[s])
+          if (++per_pool[plan->node_pool[c]] > bg->allowed[plan->node_pool[c]]) blocked[s] = 1;
+        if (blocked[s]) continue;  // neither batched nor compiled: the zero no-op
+      }
       bool ok = batch_on && plan->gb;
       if (ok && plan->gb->C->G) {  // an inverse anti-affinity group would vanish: the per-subset compile
         const Compiled& C = *plan->gb->C;
@@ -6362,7 +6414,13 @@ static int32_t GeneralSimLocked(kp_cluster_plan* plan, const uint32_t* offsets, 
       batchable[s] = ok ? 1 : 0;
     }
   });
-  for (uint32_t s = 0; s < n_subsets; s++) (batchable[s] ? batched : single).push_back((int)s);
+  for (uint32_t s = 0; s < n_subsets; s++) {
+    if (blocked[s]) {
+      bg->blocked++;
+      continue;
+    }
+    (batchable[s] ? batched : single).push_back((int)s);
+  }
   const auto t1 = clk::now();
   if (!batched.empty()) {
     const int32_t rc = GeneralBatchRun(plan, *plan->gb, cands, batched, labels, multi_node, outs, counters, &dev_ms, host_ms,
@@ -6402,11 +6460,15 @@ static int32_t GeneralSimLocked(kp_cluster_plan* plan, const uint32_t* offsets, 
 }
 
 static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, const uint32_t* nodes, uint32_t n_subsets,
-                               int32_t multi_node, SimArgs& a_out, kp_cancel* cancel) {
+                               int32_t multi_node, SimArgs& a_out, kp_cancel* cancel, BudgetGate* bg = nullptr) {
   kp_ctx* ctx = plan->ctx;
   if (cancel && __atomic_load_n(cancel->flag, __ATOMIC_SEQ_CST))
     return fail(KP_E_CANCELED, "cancelled before the simulations");
-  if (plan->general) return GeneralSimLocked(plan, offsets, nodes, n_subsets, multi_node, a_out, cancel);
+  if (bg) {
+    if (int32_t rc = CheckBudget(plan, bg)) return rc;
+    bg->blocked = 0;
+  }
+  if (plan->general) return GeneralSimLocked(plan, offsets, nodes, n_subsets, multi_node, a_out, cancel, bg);
   if (int32_t rc = CatalogsAlive(plan->cp->B->alive)) return rc;
   if (SeqnumsOf(plan->cp->B->catalogs) != plan->cp->B->seqnums)
     return fail(KP_E_INVAL, "stale plan: a catalogue's seqnum changed since it was prepared (kp_cluster_refresh)");
@@ -6421,6 +6483,8 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
     for (uint32_t j = offsets[s]; j < offsets[s + 1]; j++) {
       if (nodes[j] >= (uint32_t)plan->N) return fail(KP_E_INVAL, "subset %u: node %u", s, nodes[j]);
       if (any_deleting && plan->deleting[nodes[j]]) return fail(KP_E_INVAL, "subset %u: node %u is being deleted", s, nodes[j]);
+      if (bg && plan->node_pool[nodes[j]] == 0xFFFF)
+        return fail(KP_E_INVAL, "subset %u: node %u has no NodePool of the cluster (karpenter.sh/nodepool)", s, nodes[j]);
       np += plan->node_npods[nodes[j]];
     }
     if (np > 65535) return fail(KP_E_UNSUPPORTED, "subset %u reschedules %llu pods (max 65535)", s, (unsigned long long)np);
@@ -6441,7 +6505,7 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
     a.cancel = (const int32_t*)dp;
   }
   hipFuncAttributes fa;
-  HIPCHK(hipFuncGetAttributes(&fa, sim_kernel_ptr()));
+  HIPCHK(hipFuncGetAttributes(&fa, sim_kernel_ptr(bg != nullptr)));
   const size_t lds_wg = fa.sharedSizeBytes + (size_t)SIM_WAVES * a.wave_lds;
   if (lds_wg > 160 * 1024) return fail(KP_E_UNSUPPORTED, "simulation LDS %zu B per workgroup (cluster or subsets too large)", lds_wg);
   const int wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds_wg));
@@ -6483,11 +6547,17 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
   // batch: subsets + results
   const size_t b_off = al(sizeof(uint32_t) * (n_subsets + 1)), b_nodes = al(sizeof(uint32_t) * std::max<uint32_t>(n_flat, 1));
   const size_t b_out = al(sizeof(SimOut) * n_subsets);
-  if (b_off + b_nodes + b_out > plan->batch_bytes) {
+  // the budget gate's regions: gate bytes, live list, block counts and offsets, allowed[], the live count
+  const uint32_t n_gblk = (n_subsets + GATE_BLOCK - 1) / GATE_BLOCK;
+  const size_t g_gate = bg ? al(n_subsets) : 0, g_live = bg ? al(sizeof(uint32_t) * n_subsets) : 0;
+  const size_t g_blk = bg ? al(sizeof(uint32_t) * n_gblk) : 0, g_allowed = bg ? al(sizeof(uint32_t) * (plan->n_pools + 1)) : 0;
+  const size_t b_total = b_off + b_nodes + b_out + g_gate + g_live + 2 * g_blk + g_allowed + (bg ? 256 : 0);
+  if (b_total > plan->batch_bytes) {
     if (plan->batch.p) HIPCHK(hipFree(plan->batch.p));
     plan->batch.p = nullptr;
-    HIPCHK(hipMalloc(&plan->batch.p, b_off + b_nodes + b_out));
-    plan->batch_bytes = b_off + b_nodes + b_out;
+    plan->batch_bytes = 0;
+    HIPCHK(hipMalloc(&plan->batch.p, b_total));
+    plan->batch_bytes = b_total;
   }
   uint8_t* bb = (uint8_t*)plan->batch.p;
   a.sub_off = (const uint32_t*)bb;
@@ -6498,6 +6568,39 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
   if (n_flat) HIPCHK(hipMemcpyAsync(bb + b_off, nodes, sizeof(uint32_t) * n_flat, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(a.s_ncfail, 0xFF, sz_fail, st));
   HIPCHK(hipMemsetAsync(a.stats, 0, sizeof(uint64_t) * 8, st));
+  if (bg) {
+    // the gate on the resident batch, then the live count (4 bytes) sizes the simulation grid
+    uint8_t* gp = bb + b_off + b_nodes + b_out;
+    GateArgs g;
+    memset(&g, 0, sizeof g);
+    g.n_subsets = (int32_t)n_subsets;
+    g.n_pools = (int32_t)plan->n_pools;
+    g.n_nodes = plan->N;
+    g.sub_off = a.sub_off;
+    g.sub_nodes = a.sub_nodes;
+    g.node_pool = plan->d_node_pool;
+    g.out = a.out;
+    g.gate = gp;
+    g.live = (uint32_t*)(gp + g_gate);
+    g.blk_cnt = (uint32_t*)(gp + g_gate + g_live);
+    g.blk_off = (uint32_t*)(gp + g_gate + g_live + g_blk);
+    g.allowed = (const uint32_t*)(gp + g_gate + g_live + 2 * g_blk);
+    g.n_live = (uint32_t*)(gp + g_gate + g_live + 2 * g_blk + g_allowed);
+    if (plan->n_pools)
+      HIPCHK(hipMemcpyAsync((void*)g.allowed, bg->allowed, sizeof(uint32_t) * plan->n_pools, hipMemcpyHostToDevice, st));
+    HIPCHK(launch_budget_gate(g, st));
+    uint32_t n_live = 0;
+    HIPCHK(hipMemcpyAsync(&n_live, g.n_live, sizeof n_live, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (n_live > n_subsets) return fail(KP_E_DEVICE, "budget gate: %u live of %u subsets", n_live, n_subsets);
+    bg->blocked = n_subsets - n_live;
+    blocks = std::max(1, std::min<int>((int)((n_live + SIM_WAVES - 1) / SIM_WAVES), blocks));
+    a.n_slots = blocks * SIM_WAVES;  // (the scratch above holds the ungated grid's slots: at least as many)
+    HIPCHK(hipEventRecord(ctx->ev0, st));
+    if (n_live) HIPCHK(launch_sim_gated(a, g.live, (int)n_live, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
+    HIPCHK(hipEventRecord(ctx->ev1, st));
+    return KP_OK;
+  }
   HIPCHK(hipEventRecord(ctx->ev0, st));
   HIPCHK(launch_sim(a, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
   HIPCHK(hipEventRecord(ctx->ev1, st));
@@ -6509,9 +6612,31 @@ int32_t kp_cluster_simulate(kp_cluster_plan* plan, const uint32_t* offsets, cons
   return kp_cluster_simulate_cancellable(plan, nullptr, offsets, nodes, n_subsets, multi_node, out, stats);
 }
 
+static int32_t SimulateImpl(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
+                            uint32_t n_subsets, int32_t multi_node, kp_sim_result* out, kp_solve_stats* stats,
+                            BudgetGate* bg);
+
 int32_t kp_cluster_simulate_cancellable(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets,
                                         const uint32_t* nodes, uint32_t n_subsets, int32_t multi_node, kp_sim_result* out,
                                         kp_solve_stats* stats) {
+  return SimulateImpl(plan, cancel, offsets, nodes, n_subsets, multi_node, out, stats, nullptr);
+}
+
+int32_t kp_cluster_simulate_budgeted(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets,
+                                     const uint32_t* nodes, uint32_t n_subsets, int32_t multi_node,
+                                     const uint32_t* allowed, uint32_t n_allowed, kp_sim_result* out, uint64_t* n_blocked,
+                                     kp_solve_stats* stats) {
+  if (n_blocked) *n_blocked = 0;
+  if (!allowed) return SimulateImpl(plan, cancel, offsets, nodes, n_subsets, multi_node, out, stats, nullptr);
+  BudgetGate bg{allowed, n_allowed};
+  const int32_t rc = SimulateImpl(plan, cancel, offsets, nodes, n_subsets, multi_node, out, stats, &bg);
+  if (!rc && n_blocked) *n_blocked = bg.blocked;
+  return rc;
+}
+
+static int32_t SimulateImpl(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
+                            uint32_t n_subsets, int32_t multi_node, kp_sim_result* out, kp_solve_stats* stats,
+                            BudgetGate* bg) {
   auto t0 = std::chrono::steady_clock::now();
   if (!plan || (n_subsets && (!offsets || !out))) return fail(KP_E_INVAL, "null argument");
   if (cancel && cancel->ctx.p != plan->ctx.p) return fail(KP_E_INVAL, "the cancel token belongs to another context");
@@ -6519,9 +6644,11 @@ int32_t kp_cluster_simulate_cancellable(kp_cluster_plan* plan, kp_cancel* cancel
   std::lock_guard<std::recursive_mutex> lock(ctx->mu);
   HIPCHK(hipSetDevice(ctx->device));
   if (stats) memset(stats, 0, sizeof *stats);
+  if (bg)
+    if (int32_t rc = CheckBudget(plan, bg)) return rc;
   if (n_subsets == 0) return KP_OK;
   SimArgs a;
-  int32_t rc = SimLaunchLocked(plan, offsets, nodes, n_subsets, multi_node, a, cancel);
+  int32_t rc = SimLaunchLocked(plan, offsets, nodes, n_subsets, multi_node, a, cancel, bg);
   if (rc) return rc;
   hipStream_t st = ctx->stream;
   uint64_t kst[8];
@@ -6701,10 +6828,34 @@ int32_t kp_consolidate_argmin(kp_cluster_plan* plan, kp_comm* comm, const uint32
                                            best, stats);
 }
 
+static int32_t ArgminImpl(kp_cluster_plan* plan, kp_comm* comm, kp_cancel* cancel, const uint32_t* offsets,
+                          const uint32_t* nodes, uint32_t n_subsets, uint64_t base_index, int32_t multi_node,
+                          kp_sim_result* out, kp_choice* best, kp_solve_stats* stats, BudgetGate* bg);
+
 int32_t kp_consolidate_argmin_cancellable(kp_cluster_plan* plan, kp_comm* comm, kp_cancel* cancel,
                                           const uint32_t* offsets, const uint32_t* nodes, uint32_t n_subsets,
                                           uint64_t base_index, int32_t multi_node, kp_sim_result* out, kp_choice* best,
                                           kp_solve_stats* stats) {
+  return ArgminImpl(plan, comm, cancel, offsets, nodes, n_subsets, base_index, multi_node, out, best, stats, nullptr);
+}
+
+int32_t kp_consolidate_argmin_budgeted(kp_cluster_plan* plan, kp_comm* comm, kp_cancel* cancel, const uint32_t* offsets,
+                                       const uint32_t* nodes, uint32_t n_subsets, uint64_t base_index, int32_t multi_node,
+                                       const uint32_t* allowed, uint32_t n_allowed, kp_sim_result* out, kp_choice* best,
+                                       uint64_t* n_blocked, kp_solve_stats* stats) {
+  if (n_blocked) *n_blocked = 0;
+  if (!allowed)
+    return ArgminImpl(plan, comm, cancel, offsets, nodes, n_subsets, base_index, multi_node, out, best, stats, nullptr);
+  BudgetGate bg{allowed, n_allowed};
+  const int32_t rc = ArgminImpl(plan, comm, cancel, offsets, nodes, n_subsets, base_index, multi_node, out, best, stats, &bg);
+  if (!rc && n_blocked) *n_blocked = bg.blocked;
+  return rc;
+}
+
+// bg: the budget gate (a failure of it is a failure of the local step: a KP_CHOICE_FAILED record, no peer left waiting)
+static int32_t ArgminImpl(kp_cluster_plan* plan, kp_comm* comm, kp_cancel* cancel, const uint32_t* offsets,
+                          const uint32_t* nodes, uint32_t n_subsets, uint64_t base_index, int32_t multi_node,
+                          kp_sim_result* out, kp_choice* best, kp_solve_stats* stats, BudgetGate* bg) {
   auto t0 = std::chrono::steady_clock::now();
   if (!plan || !best || (n_subsets && !offsets)) return fail(KP_E_INVAL, "null argument");
   if (cancel && cancel->ctx.p != plan->ctx.p) return fail(KP_E_INVAL, "the cancel token belongs to another context");
@@ -6727,8 +6878,10 @@ int32_t kp_consolidate_argmin_cancellable(kp_cluster_plan* plan, kp_comm* comm, 
     const int n_parts = (int)std::min<uint32_t>(std::max<uint32_t>((n_subsets + 4095) / 4096, 1), 1024);
     HIPCHK(parts.alloc(sizeof(ArgmaxPart) * n_parts));
     HIPCHK(rec.alloc(sizeof(CommBest)));
+    if (bg)
+      if (int32_t rc = CheckBudget(plan, bg)) return rc;
     if (n_subsets) {
-      int32_t rc = SimLaunchLocked(plan, offsets, nodes, n_subsets, multi_node, a, cancel);
+      int32_t rc = SimLaunchLocked(plan, offsets, nodes, n_subsets, multi_node, a, cancel, bg);
       if (rc) return rc;
       if (out) HIPCHK(hipMemcpyAsync(out, a.out, sizeof(SimOut) * n_subsets, hipMemcpyDeviceToHost, st));
       HIPCHK(hipMemcpyAsync(kst, a.stats, sizeof kst, hipMemcpyDeviceToHost, st));

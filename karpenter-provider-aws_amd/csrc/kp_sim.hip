@@ -25,6 +25,9 @@
 //                                       result a no-op, so the simulation stops there.
 //                     then the decision: TruncateInstanceTypes (cheapest compatible offering, name; LDS
 //                     bitonic sort) + minValues, filterByPrice on WorstLaunchPrice, filterOutSameType.
+//  budget_gate_kernel NodePool disruption budgets (kp_*_budgeted), before sim_kernel: per subset the members per owning
+//                     NodePool against allowed[]; the admissible subsets' ascending index list (gate_scan_kernel,
+//                     gate_scatter_kernel) is what the gated sim_kernel instantiation walks (end of this file).
 //
 // The host routes the clusters these kernels do not model to the general path (each subset a whole device Solve,
 // batched one workgroup per subset on the cluster's superset Solve: kp_host.cpp GeneralBatch): topology spread and pod (anti-)affinity, a pod NotIn/DoesNotExist requirement on a
@@ -264,8 +267,11 @@ __global__ __launch_bounds__(SIM_WAVES * 64) void sim_prep_kernel(SimArgs a) {
 #else
 #define SIM_OCCUPANCY
 #endif
-template <int NW>
-__global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a) {
+// GL = SimLive is the gated instantiation (kp_*_budgeted): a.n_subsets counts the admissible subsets and the k-th
+// simulation is subset gl.live[k] (ascending: budget_gate_kernel). GL = SimAll walks every subset; its conditionals on
+// GL::gated fold away before code generation, so that instantiation compiles as it did without the gate.
+template <int NW, class GL>
+__global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, GL gl) {
   __shared__ DevDict D;
   __shared__ WaveSlots slots[NW];
   __shared__ KReqs s_B[NW];
@@ -317,8 +323,8 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a) {
       cancelled = true;
       break;
     }
-    const uint32_t s0 = a.sub_off[sim];
-    const int ns = (int)(a.sub_off[sim + 1] - s0);
+    const uint32_t s0 = a.sub_off[GL::gated ? (int)gl.live[sim] : sim];
+    const int ns = (int)(a.sub_off[(GL::gated ? (int)gl.live[sim] : sim) + 1] - s0);
     for (int w = lane; w < EW; w += 64) {
       excl[w] = a.base_excl[w];  // deleting nodes are never destinations
       dirty[w] = 0;
@@ -712,7 +718,7 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a) {
       o.savings = savings;
       o.n_options = (uint32_t)(decision == KP_DECISION_REPLACE ? n_options : 0);
       o.n_pods = overflow ? 0xFFFFFFFFu : (uint32_t)n;
-      a.out[sim] = o;
+      a.out[GL::gated ? (int)gl.live[sim] : sim] = o;
     }
     sim_sync();
   }
@@ -737,10 +743,19 @@ hipError_t launch_sim_prep(const SimArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 hipError_t launch_sim(const SimArgs& a, int blocks, size_t dyn_lds, hipStream_t s) {
-  hipLaunchKernelGGL(sim_kernel<SIM_WAVES>, dim3(blocks), dim3(SIM_WAVES * 64), dyn_lds, s, a);
+  hipLaunchKernelGGL((sim_kernel<SIM_WAVES, SimAll>), dim3(blocks), dim3(SIM_WAVES * 64), dyn_lds, s, a, SimAll{});
   return hipGetLastError();
 }
-const void* sim_kernel_ptr() { return reinterpret_cast<const void*>(sim_kernel<SIM_WAVES>); }
+hipError_t launch_sim_gated(const SimArgs& a, const uint32_t* live, int n_live, int blocks, size_t dyn_lds, hipStream_t s) {
+  SimArgs al = a;
+  al.n_subsets = n_live;
+  hipLaunchKernelGGL((sim_kernel<SIM_WAVES, SimLive>), dim3(blocks), dim3(SIM_WAVES * 64), dyn_lds, s, al, SimLive{live});
+  return hipGetLastError();
+}
+const void* sim_kernel_ptr(bool gated) {
+  return gated ? reinterpret_cast<const void*>(sim_kernel<SIM_WAVES, SimLive>)
+               : reinterpret_cast<const void*>(sim_kernel<SIM_WAVES, SimAll>);
+}
 
 // ------------------------------------------------------------------------------------------------
 // Best decision of a simulated batch (kp_consolidate_argmin): max savings over non-no-op decisions, ties to the
@@ -827,5 +842,123 @@ hipError_t launch_argmax(const SimOut* out, int n, ArgmaxPart* part, int n_parts
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(ARGMAX_THREADS), 0, s, part, n > 0 ? n_parts : 0, out, base, dst);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// NodePool disruption budgets (kp_cluster_simulate_budgeted / kp_consolidate_argmin_budgeted): a subset is admissible
+// iff no NodePool owns more of its members than allowed[pool] (R:website/content/en/preview/concepts/disruption.md:
+// 274-333). The gate runs over the resident CSR batch before sim_kernel and leaves, besides the per-subset gate byte
+// and the zero no-op of every blocked subset, the ascending list live[] of the admissible ones, which the gated
+// sim_kernel walks. The list is built order-preserving (count per block, scan of the block counts in one block,
+// scatter), so which wave simulates which subset is the same from run to run.
+// ------------------------------------------------------------------------------------------------
+static_assert(GATE_BLOCK == 64, "gate_scatter_kernel: one wave per block of the gate");
+// One subset per wave at a time, GATE_PER_WAVE consecutive subsets per wave. Members are loaded 64 at a time
+// (coalesced over sub_nodes), their pools gathered from the node table, and the per-pool counts of the chunk taken
+// from the wave's own ballot: the first pending lane's pool, the lanes that share it, their popcount; per-wave LDS
+// counters carry the counts across chunks.
+__global__ __launch_bounds__(GATE_WAVES * 64) void budget_gate_kernel(GateArgs g) {
+  __shared__ uint32_t s_cnt[GATE_WAVES][GATE_MAX_POOLS];
+  __shared__ uint32_t s_adm[GATE_WAVES];
+  const int wave = threadIdx.x >> 6, lane = LANE;
+  uint32_t* cnt = s_cnt[wave];
+  const int n_pools = min(g.n_pools, GATE_MAX_POOLS);
+  const int first = blockIdx.x * GATE_BLOCK + wave * GATE_PER_WAVE;
+  uint32_t adm = 0;
+  for (int k = 0; k < GATE_PER_WAVE; k++) {
+    const int sim = first + k;
+    if (sim >= g.n_subsets) break;
+    for (int q = lane; q < n_pools; q += 64) cnt[q] = 0;
+    wave_sync();
+    const uint32_t s0 = g.sub_off[sim], ns = g.sub_off[sim + 1] - s0;
+    for (uint32_t i0 = 0; i0 < ns; i0 += 64) {
+      const uint32_t i = i0 + lane;
+      const bool valid = i < ns;
+      uint32_t p = 0xFFFFu;
+      if (valid) {
+        const uint32_t c = g.sub_nodes[s0 + i];
+        if (c < (uint32_t)g.n_nodes) p = g.node_pool[c];
+      }
+      uint64_t todo = __ballot(valid);
+      while (todo) {
+        const int L = __builtin_ctzll(todo);
+        const uint32_t pl = (uint32_t)__builtin_amdgcn_readlane((int)p, L);
+        const uint64_t same = __ballot(valid && p == pl);
+        if (lane == 0 && pl < (uint32_t)n_pools) cnt[pl] += (uint32_t)__builtin_popcountll(same);
+        todo &= ~same;
+      }
+    }
+    wave_sync();
+    bool over = false;
+    for (int q = lane; q < n_pools; q += 64) over = over || cnt[q] > g.allowed[q];
+    const bool ok = __ballot(over) == 0;
+    if (lane == 0) {
+      g.gate[sim] = ok ? 1 : 0;
+      if (!ok) {  // a blocked subset is not simulated: the zero no-op
+        SimOut o;
+        o.decision = KP_DECISION_NOOP;
+        o.nodepool = 0;
+        o.candidate_price = 0;
+        o.replacement_price = 0;
+        o.savings = 0;
+        o.n_options = 0;
+        o.n_pods = 0;
+        g.out[sim] = o;
+      }
+    }
+    adm += ok ? 1u : 0u;
+    wave_sync();
+  }
+  if (lane == 0) s_adm[wave] = adm;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t t = 0;
+    for (int w = 0; w < GATE_WAVES; w++) t += s_adm[w];
+    g.blk_cnt[blockIdx.x] = t;
+  }
+}
+// one block: exclusive scan of the gate blocks' counts, and the live count
+#define GATE_SCAN_THREADS 256
+__global__ __launch_bounds__(GATE_SCAN_THREADS) void gate_scan_kernel(GateArgs g, int nb) {
+  __shared__ uint32_t s_sum[GATE_SCAN_THREADS];
+  const int tid = threadIdx.x;
+  const int per = (nb + GATE_SCAN_THREADS - 1) / GATE_SCAN_THREADS;
+  const int lo = min(nb, tid * per), hi = min(nb, lo + per);
+  uint32_t s = 0;
+  for (int i = lo; i < hi; i++) s += g.blk_cnt[i];
+  s_sum[tid] = s;
+  __syncthreads();
+  for (int d = 1; d < GATE_SCAN_THREADS; d <<= 1) {
+    const uint32_t v = tid >= d ? s_sum[tid - d] : 0;
+    __syncthreads();
+    s_sum[tid] += v;
+    __syncthreads();
+  }
+  uint32_t run = s_sum[tid] - s;
+  for (int i = lo; i < hi; i++) {
+    g.blk_off[i] = run;
+    run += g.blk_cnt[i];
+  }
+  if (tid == GATE_SCAN_THREADS - 1) *g.n_live = s_sum[tid];
+}
+// one wave per gate block: its admissible subsets, in order, behind those of the blocks before it
+__global__ __launch_bounds__(64) void gate_scatter_kernel(GateArgs g) {
+  const int lane = LANE;
+  const int sim = blockIdx.x * GATE_BLOCK + lane;
+  const bool ok = sim < g.n_subsets && g.gate[sim] != 0;
+  const uint64_t bal = __ballot(ok);
+  if (ok) g.live[g.blk_off[blockIdx.x] + __builtin_popcountll(bal & ((1ull << lane) - 1))] = (uint32_t)sim;
+}
+hipError_t launch_budget_gate(const GateArgs& g, hipStream_t s) {
+  const int nb = (g.n_subsets + GATE_BLOCK - 1) / GATE_BLOCK;
+  if (nb < 1 || g.n_pools > GATE_MAX_POOLS) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(budget_gate_kernel, dim3(nb), dim3(GATE_WAVES * 64), 0, s, g);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(gate_scan_kernel, dim3(1), dim3(GATE_SCAN_THREADS), 0, s, g, nb);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(gate_scatter_kernel, dim3(nb), dim3(64), 0, s, g);
   return hipGetLastError();
 }

@@ -110,6 +110,13 @@ def load_lib(path=None):
                                                           P(C.c_uint32), C.c_uint32, C.c_uint64, C.c_int32,
                                                           P(abi.SimResult), P(abi.Choice), P(abi.SolveStats)]),
         "kp_choice_reduce": (C.c_int32, [P(abi.Choice), C.c_uint32, P(abi.Choice)]),
+        "kp_cluster_simulate_budgeted": (C.c_int32, [C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32), C.c_uint32,
+                                                     C.c_int32, P(C.c_uint32), C.c_uint32, P(abi.SimResult),
+                                                     P(C.c_uint64), P(abi.SolveStats)]),
+        "kp_consolidate_argmin_budgeted": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32),
+                                                       C.c_uint32, C.c_uint64, C.c_int32, P(C.c_uint32), C.c_uint32,
+                                                       P(abi.SimResult), P(abi.Choice), P(C.c_uint64),
+                                                       P(abi.SolveStats)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name, None)
@@ -591,37 +598,59 @@ class ClusterPlan:
         """kp_cluster_refresh: re-apply the catalogues' current offerings (after update_offerings) in place."""
         _check(self.ctx.lib, self.ctx.lib.kp_cluster_refresh(self.h))
 
-    def simulate(self, subsets, multi_node=True, raw=False, cancel=None):
+    @staticmethod
+    def _allowed(allowed):
+        arr = np.ascontiguousarray(allowed, dtype=np.uint32)
+        return arr, arr.ctypes.data_as(C.POINTER(C.c_uint32)), len(arr)
+
+    def _simulate(self, cancel, offs, flat, n, multi_node, out, st, allowed):
+        """kp_cluster_simulate_cancellable, or with allowed (disruption.allowed_disruptions) kp_cluster_simulate_budgeted;
+        returns the stats dict (with budget_blocked when allowed is given)."""
+        lib, ch = self.ctx.lib, cancel.h if cancel is not None else None
+        if allowed is None:
+            _check(lib, lib.kp_cluster_simulate_cancellable(self.h, ch, offs, flat, n, 1 if multi_node else 0, out,
+                                                            C.byref(st)))
+            return stats_dict(st)
+        keep, ap, na = self._allowed(allowed)
+        blocked = C.c_uint64(0)
+        _check(lib, lib.kp_cluster_simulate_budgeted(self.h, ch, offs, flat, n, 1 if multi_node else 0, ap, na, out,
+                                                     C.byref(blocked), C.byref(st)))
+        return dict(stats_dict(st), budget_blocked=int(blocked.value))
+
+    def simulate(self, subsets, multi_node=True, raw=False, cancel=None, allowed=None):
         """subsets: list of node-index lists (candidate order). Returns (results, stats); raw=True returns
-        the kp_sim_result array instead of dicts. cancel: a Cancel token (kp_cluster_simulate_cancellable)."""
+        the kp_sim_result array instead of dicts. cancel: a Cancel token (kp_cluster_simulate_cancellable). allowed:
+        allowed disruptions per NodePool (kp_cluster_simulate_budgeted; stats gain budget_blocked)."""
         arena = Arena()
         offs, flat = abi.subsets_csr(arena, subsets)
         out = (abi.SimResult * max(1, len(subsets)))()
         st = abi.SolveStats()
-        _check(self.ctx.lib, self.ctx.lib.kp_cluster_simulate_cancellable(
-            self.h, cancel.h if cancel is not None else None, offs, flat, len(subsets), 1 if multi_node else 0,
-            out, C.byref(st)))
+        sd = self._simulate(cancel, offs, flat, len(subsets), multi_node, out, st, allowed)
         if raw:
-            return out, stats_dict(st)
-        return [sim_dict(out[i]) for i in range(len(subsets))], stats_dict(st)
+            return out, sd
+        return [sim_dict(out[i]) for i in range(len(subsets))], sd
 
-    def simulate_csr(self, offsets, nodes, multi_node=True, cancel=None):
-        """CSR batch (uint32 offsets[n+1], node indices) -> numpy structured array (abi.sim_dtype()), stats."""
+    def simulate_csr(self, offsets, nodes, multi_node=True, cancel=None, allowed=None):
+        """CSR batch (uint32 offsets[n+1], node indices) -> numpy structured array (abi.sim_dtype()), stats. allowed: as
+        simulate()."""
         offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
         nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
         n = len(offsets) - 1
         out = np.zeros(max(n, 1), dtype=abi.sim_dtype())
         st = abi.SolveStats()
         P = C.POINTER
-        _check(self.ctx.lib, self.ctx.lib.kp_cluster_simulate_cancellable(
-            self.h, cancel.h if cancel is not None else None, offsets.ctypes.data_as(P(C.c_uint32)), nodes.ctypes.data_as(P(C.c_uint32)) if len(nodes) else None,
-            n, 1 if multi_node else 0, out.ctypes.data_as(P(abi.SimResult)), C.byref(st)))
-        return out[:n], stats_dict(st)
+        sd = self._simulate(cancel, offsets.ctypes.data_as(P(C.c_uint32)),
+                            nodes.ctypes.data_as(P(C.c_uint32)) if len(nodes) else None, n, multi_node,
+                            out.ctypes.data_as(P(abi.SimResult)), st, allowed)
+        return out[:n], sd
 
-    def argmin(self, offsets, nodes, base_index=0, comm=None, multi_node=True, read_all=False, cancel=None):
+    def argmin(self, offsets, nodes, base_index=0, comm=None, multi_node=True, read_all=False, cancel=None,
+               allowed=None):
         """kp_consolidate_argmin: this rank's subsets (CSR, global indices base_index + i) simulated, reduced on the
         device and across ranks (RCCL all-gather when comm is a Comm). Returns (choice dict, per-subset results
-        or None, stats). cancel: a Cancel token (kp_consolidate_argmin_cancellable)."""
+        or None, stats). cancel: a Cancel token (kp_consolidate_argmin_cancellable). allowed: allowed disruptions per
+        NodePool (kp_consolidate_argmin_budgeted): the subsets over a pool's allowance are gated out on the device and
+        stats gain budget_blocked (this rank's count)."""
         offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
         nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
         n = len(offsets) - 1
@@ -629,12 +658,20 @@ class ClusterPlan:
         ch = abi.Choice()
         st = abi.SolveStats()
         P = C.POINTER
-        _check(self.ctx.lib, self.ctx.lib.kp_consolidate_argmin_cancellable(
-            self.h, comm.h if comm is not None else None, cancel.h if cancel is not None else None,
-            offsets.ctypes.data_as(P(C.c_uint32)),
-            nodes.ctypes.data_as(P(C.c_uint32)) if len(nodes) else None, n, int(base_index), 1 if multi_node else 0,
-            out.ctypes.data_as(P(abi.SimResult)) if out is not None else None, C.byref(ch), C.byref(st)))
-        return choice_dict(ch), (out[:n] if out is not None else None), stats_dict(st)
+        head = (self.h, comm.h if comm is not None else None, cancel.h if cancel is not None else None,
+                offsets.ctypes.data_as(P(C.c_uint32)), nodes.ctypes.data_as(P(C.c_uint32)) if len(nodes) else None, n,
+                int(base_index), 1 if multi_node else 0)
+        outp = out.ctypes.data_as(P(abi.SimResult)) if out is not None else None
+        if allowed is None:
+            _check(self.ctx.lib, self.ctx.lib.kp_consolidate_argmin_cancellable(*head, outp, C.byref(ch), C.byref(st)))
+            sd = stats_dict(st)
+        else:
+            keep, ap, na = self._allowed(allowed)
+            blocked = C.c_uint64(0)
+            _check(self.ctx.lib, self.ctx.lib.kp_consolidate_argmin_budgeted(*head, ap, na, outp, C.byref(ch),
+                                                                             C.byref(blocked), C.byref(st)))
+            sd = dict(stats_dict(st), budget_blocked=int(blocked.value))
+        return choice_dict(ch), (out[:n] if out is not None else None), sd
 
     def close(self):
         if self.h:

@@ -278,6 +278,7 @@ class Choice(C.Structure):
 
 COMM_ID_BYTES = 128
 CHOICE_FAILED = -2  # kp_choice.subset of a rank whose step failed
+BUDGET_UNLIMITED = 0xFFFFFFFF  # KP_BUDGET_UNLIMITED: allowed[pool] of a NodePool no active budget limits
 AllGatherFn = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t)
 
 

@@ -22,11 +22,33 @@ CS3 and R:website/content/en/preview/concepts/disruption.md:89-128):
                                             exercises, in upstream order (Emptiness, MultiNodeConsolidation,
                                             SingleNodeConsolidation): the first method that returns a command wins
 
+NodePool disruption budgets (R:website/content/en/preview/concepts/disruption.md:274-333,
+R:pkg/apis/crds/karpenter.sh_nodepools.yaml:95-135), modelled when a NodePool carries `budgets`:
+
+  allowed_disruptions(cluster, reason)      per NodePool: max(0, min over the active budgets that list the reason (or
+                                            none) of value(budget, total) - deleting - not_ready); UNLIMITED without one
+  budget_active(budget, now)                schedule + duration: the schedule's first fire time strictly after
+                                            now - duration is <= now (five-field cron or @macro, UTC)
+  budget_walk(cluster, candidates, allowed) upstream's construction for every method: the candidates in disruption-cost
+                                            order, one allowance taken from its pool per candidate kept
+  admissible(cluster, offsets, nodes, allowed)  the sweep's generalisation: a subset is admissible iff no NodePool owns
+                                            more of its members than allowed[pool] (what the device gate computes)
+
+Emptiness asks with the reason Empty, single- and multi-node consolidation with Underutilized. NodePool.budgets None is
+"not modelled": unlimited, and nothing above runs.
+
 Decisions are kp_decision values: 0 no-op, 1 delete, 2 replace.
 """
+import calendar
+import datetime
+import re
+
 import numpy as np
 
 NOOP, DELETE, REPLACE = 0, 1, 2
+UNLIMITED = 2**32 - 1  # KP_BUDGET_UNLIMITED
+POOL_LABEL = "karpenter.sh/nodepool"
+EMPTY, UNDERUTILIZED, DRIFTED = "Empty", "Underutilized", "Drifted"
 
 
 class Command:
@@ -52,12 +74,200 @@ def candidate_order(cluster, nodes=None):
     return sorted(idx, key=lambda i: (len(cluster.nodes[i].pods), cluster.nodes[i].node.name))
 
 
+# ---- NodePool disruption budgets -----------------------------------------------------------------------------------
+_NODES_RE = re.compile(r"^((100|[0-9]{1,2})%|[0-9]+)$")  # the CRD's pattern
+_MACROS = {"@yearly": "0 0 1 1 *", "@annually": "0 0 1 1 *", "@monthly": "0 0 1 * *", "@weekly": "0 0 * * 0",
+           "@daily": "0 0 * * *", "@midnight": "0 0 * * *", "@hourly": "0 * * * *"}
+_FIELDS = ((0, 59), (0, 23), (1, 31), (1, 12), (0, 7))  # minute, hour, day of month, month, day of week (7 = Sunday)
+
+
+def budget_value(nodes, total):
+    """value(budget, total): ceil(total * p / 100) for "p%", else the integer."""
+    if not isinstance(nodes, str) or not _NODES_RE.match(nodes):
+        raise ValueError(f"budget nodes {nodes!r}")
+    if nodes.endswith("%"):
+        return (total * int(nodes[:-1]) + 99) // 100
+    return int(nodes)
+
+
+def _cron_field(text, lo, hi):
+    """One cron field (`*`, lists, ranges, /step) -> (set of values, restricted?). Names are rejected."""
+    out = set()
+    for part in text.split(","):
+        rng, _, step = part.partition("/")
+        if ("/" in part and not step.isdigit()) or (step and int(step) < 1):
+            raise ValueError(f"cron step in {text!r}")
+        st = int(step) if step else 1
+        if rng == "*":
+            a, b = lo, hi
+        elif "-" in rng:
+            x, _, y = rng.partition("-")
+            if not (x.isdigit() and y.isdigit()):
+                raise ValueError(f"cron range {rng!r}")
+            a, b = int(x), int(y)
+        else:
+            if not rng.isdigit():
+                raise ValueError(f"cron value {rng!r}")
+            a = int(rng)
+            b = hi if step else a  # "a/step": from a to the field's end
+        if a < lo or b > hi or a > b:
+            raise ValueError(f"cron field {text!r} outside {lo}-{hi}")
+        out.update(range(a, b + 1, st))
+    star = text == "*" or text.startswith("*/")
+    return out, not star
+
+
+def parse_schedule(schedule):
+    """Five-field cron or @macro -> (minutes, hours, days of month, months, days of week (0-6), dom restricted, dow
+    restricted). ValueError on anything else (month and day names included)."""
+    if not isinstance(schedule, str):
+        raise ValueError(f"schedule {schedule!r}")
+    text = schedule.strip()
+    if text.startswith("@"):
+        if text not in _MACROS:
+            raise ValueError(f"schedule macro {schedule!r}")
+        text = _MACROS[text]
+    parts = text.split()
+    if len(parts) != 5:
+        raise ValueError(f"schedule {schedule!r}: five fields expected")
+    sets, restricted = [], []
+    for p, (lo, hi) in zip(parts, _FIELDS):
+        s, r = _cron_field(p, lo, hi)
+        sets.append(s)
+        restricted.append(r)
+    dow = {d % 7 for d in sets[4]}
+    return sets[0], sets[1], sets[2], sets[3], dow, restricted[2], restricted[4]
+
+
+def _ts(now):
+    if now is None:
+        return datetime.datetime.now(datetime.timezone.utc).timestamp()
+    if isinstance(now, datetime.datetime):
+        if now.tzinfo is None:
+            now = now.replace(tzinfo=datetime.timezone.utc)
+        return now.timestamp()
+    return now
+
+
+def schedule_next(schedule, after):
+    """The schedule's first fire time (unix seconds, UTC) strictly after `after`; None if none within eight years."""
+    mins, hours, doms, months, dows, dom_r, dow_r = parse_schedule(schedule)
+    t = (int(after // 60) + 1) * 60
+    end = t + 8 * 366 * 86400
+    while t < end:
+        y, mo, d, h, mi = datetime.datetime.fromtimestamp(t, datetime.timezone.utc).timetuple()[:5]
+        if mo not in months:
+            t = calendar.timegm((y + (mo == 12), mo % 12 + 1, 1, 0, 0, 0))
+            continue
+        wd = (calendar.weekday(y, mo, d) + 1) % 7  # 0 = Sunday
+        # both day fields restricted: either one matching suffices; otherwise both must match
+        day = (d in doms or wd in dows) if (dom_r and dow_r) else (d in doms and wd in dows)
+        if not day:
+            t = calendar.timegm((y, mo, d, 0, 0, 0)) + 86400
+        elif h not in hours:
+            t = calendar.timegm((y, mo, d, h, 0, 0)) + 3600
+        elif mi not in mins:
+            t += 60
+        else:
+            return t
+    return None
+
+
+def budget_active(budget, now=None):
+    """A budget without schedule and duration is always active; with both, iff the schedule's first fire time strictly
+    after now - duration is <= now (UTC). One without the other is a ValueError."""
+    if (budget.schedule is None) != (budget.duration_s is None):
+        raise ValueError("budget schedule and duration must be set together")
+    if budget.schedule is None:
+        return True
+    now = _ts(now)
+    nxt = schedule_next(budget.schedule, now - budget.duration_s)
+    return nxt is not None and nxt <= now
+
+
+def _pool_index(cluster):
+    return {p.name: i for i, p in enumerate(cluster.nodepools)}
+
+
+def node_pools(cluster):
+    """Per node: the index of the NodePool its karpenter.sh/nodepool label names, -1 if missing or unknown."""
+    idx = _pool_index(cluster)
+    return np.array([idx.get(n.node.labels.get(POOL_LABEL), -1) for n in cluster.nodes], dtype=np.int64)
+
+
+def allowed_disruptions(cluster, reason, now=None, not_ready=(), extra_deleting=None):
+    """Allowed disruptions per NodePool for `reason` (list, UNLIMITED where no active budget applies). total = the
+    pool's nodes, deleting ones included; not_ready: node indices that are NotReady; extra_deleting[pool index or
+    name]: nodes still terminating but no longer in the snapshot (they add to total and to deleting)."""
+    pools = node_pools(cluster)
+    P = len(cluster.nodepools)
+    total, busy = [0] * P, [0] * P
+    nr = set(not_ready)
+    for i, n in enumerate(cluster.nodes):
+        p = int(pools[i])
+        if p < 0:
+            continue
+        total[p] += 1
+        if n.deleting or i in nr:
+            busy[p] += 1
+    for k, v in (extra_deleting or {}).items():
+        p = k if isinstance(k, int) else _pool_index(cluster)[k]
+        total[p] += int(v)
+        busy[p] += int(v)
+    out = []
+    for p, pool in enumerate(cluster.nodepools):
+        vals = [budget_value(b.nodes, total[p]) for b in (pool.budgets or [])
+                if (b.reasons is None or reason in b.reasons) and budget_active(b, now)]
+        out.append(min(UNLIMITED, max(0, min(vals) - busy[p])) if vals else UNLIMITED)
+    return out
+
+
+def budgets_modelled(cluster):
+    return any(p.budgets is not None for p in cluster.nodepools)
+
+
+def budget_walk(cluster, candidates, allowed):
+    """Upstream's candidate construction under budgets: the candidates in the given (disruption-cost) order; one whose
+    pool has no allowance left is skipped, otherwise it is kept and takes one from its pool."""
+    pools = node_pools(cluster)
+    left = list(allowed)
+    out = []
+    for c in candidates:
+        p = int(pools[c])
+        if p < 0:
+            raise ValueError(f"node {c}: no NodePool for its {POOL_LABEL} label")
+        if left[p] == 0:
+            continue
+        if left[p] != UNLIMITED:
+            left[p] -= 1
+        out.append(c)
+    return out
+
+
+def admissible(cluster, offsets, nodes, allowed):
+    """numpy bool per CSR subset: for every NodePool, the subset's members owned by it number <= allowed[pool]."""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    nodes = np.asarray(nodes, dtype=np.int64)
+    n, P = len(offsets) - 1, len(cluster.nodepools)
+    if len(allowed) != P:
+        raise ValueError(f"allowed has {len(allowed)} entries for {P} NodePools")
+    pool = node_pools(cluster)[nodes] if len(nodes) else np.zeros(0, dtype=np.int64)
+    if (pool < 0).any():
+        raise ValueError(f"node {int(nodes[np.argmax(pool < 0)])}: no NodePool for its {POOL_LABEL} label")
+    sub = np.repeat(np.arange(n), np.diff(offsets))
+    cnt = np.zeros((n, max(P, 1)), dtype=np.int64)
+    np.add.at(cnt, (sub, pool), 1)
+    return (cnt[:, :P] <= np.asarray(allowed, dtype=np.int64)[None, :]).all(axis=1)
+
+
 class Emptiness:
     """Emptiness (WhenEmptyOrUnderutilized with consolidateAfter elapsed): every candidate node without reschedulable
-    pods is deleted, all in one command (disruption budgets are not modelled: 100 %)."""
+    pods is deleted, all in one command; under budgets, as many as the reason Empty allows per NodePool (the walk)."""
 
-    def compute_command(self, cluster, candidates):
+    def compute_command(self, cluster, candidates, now=None, not_ready=(), extra_deleting=None):
         empty = [c for c in candidates if not cluster.nodes[c].pods]
+        if empty and budgets_modelled(cluster):
+            empty = budget_walk(cluster, empty, allowed_disruptions(cluster, EMPTY, now, not_ready, extra_deleting))
         return Command("emptiness", empty, DELETE, {"decision": DELETE}) if empty else None
 
 
@@ -65,31 +275,48 @@ class Controller:
     """One pass of the disruption controller over the consolidation methods, in upstream order: Emptiness, then
     MultiNodeConsolidation (firstNConsolidationOption over the disruption-cost order), then SingleNodeConsolidation
     (the first candidate whose computeConsolidation is not a no-op). plan: the resident snapshot of `cluster`
-    (ClusterPlan, or any object with the same simulate(subsets, multi_node))."""
+    (ClusterPlan, or any object with the same simulate(subsets, multi_node)). When some NodePool has budgets, each
+    method's candidates go through the budget walk first (Emptiness: reason Empty, the others: Underutilized); now,
+    not_ready and extra_deleting are allowed_disruptions' arguments."""
 
-    def compute_command(self, cluster, plan):
+    def compute_command(self, cluster, plan, now=None, not_ready=(), extra_deleting=None):
         cands = candidate_order(cluster)
-        cmd = Emptiness().compute_command(cluster, cands)
+        cmd = Emptiness().compute_command(cluster, cands, now, not_ready, extra_deleting)
         if cmd is not None:
             return cmd
         cands = [c for c in cands if cluster.nodes[c].pods]
-        hit = MultiNodeConsolidation(plan).first_n_option(cands)
+        allowed = None
+        if budgets_modelled(cluster):
+            allowed = allowed_disruptions(cluster, UNDERUTILIZED, now, not_ready, extra_deleting)
+        multi = MultiNodeConsolidation(plan, cluster, allowed)
+        hit = multi.first_n_option(cands)
         if hit is not None:
             n, r = hit
-            return Command("multi", cands[:n], r["decision"], r)
-        hit = SingleNodeConsolidation(plan).compute_command(cands)
+            return Command("multi", multi.candidates(cands)[:n], r["decision"], r)
+        hit = SingleNodeConsolidation(plan, cluster, allowed).compute_command(cands)
         if hit is not None:
             c, r = hit
             return Command("single", [c], r["decision"], r)
         return None
 
 
-class SingleNodeConsolidation:
-    def __init__(self, plan):
-        self.plan = plan
+class _Budgeted:
+    """A consolidation method over plan; with allowed (allowed_disruptions of cluster) its candidates are the budget
+    walk's."""
 
+    def __init__(self, plan, cluster=None, allowed=None):
+        self.plan, self.cluster, self.allowed = plan, cluster, allowed
+
+    def candidates(self, candidates):
+        if self.allowed is None:
+            return list(candidates)
+        return budget_walk(self.cluster, candidates, self.allowed)
+
+
+class SingleNodeConsolidation(_Budgeted):
     def compute_command(self, candidates):
         """Returns (candidate, result) of the first candidate whose simulation is not a no-op, or None."""
+        candidates = self.candidates(candidates)
         if not candidates:
             return None
         res, _ = self.plan.simulate([[c] for c in candidates], multi_node=False)
@@ -99,11 +326,8 @@ class SingleNodeConsolidation:
         return None
 
 
-class MultiNodeConsolidation:
+class MultiNodeConsolidation(_Budgeted):
     MAX_PARALLEL = 100  # upstream MultiNodeConsolidation MaxParallel
-
-    def __init__(self, plan):
-        self.plan = plan
 
     @staticmethod
     def search_hi(n):
@@ -137,7 +361,9 @@ class MultiNodeConsolidation:
         return best
 
     def first_n_option(self, candidates):
-        """Returns (prefix length, result) of the command firstNConsolidationOption picks, or None."""
+        """Returns (prefix length, result) of the command firstNConsolidationOption picks, or None; the prefix is of
+        self.candidates(candidates), the budget walk's list."""
+        candidates = self.candidates(candidates)
         mids = self.search_prefixes(len(candidates))
         if not mids:
             return None
@@ -247,9 +473,13 @@ def _as_struct(results):
     return out
 
 
-def sweep(plan, offsets, nodes, base_index=0, comm=None, multi_node=True):
+def sweep(plan, offsets, nodes, base_index=0, comm=None, multi_node=True, allowed=None):
     """The config-4 sweep step of one rank: kp_consolidate_argmin over this rank's CSR subsets (global indices
     base_index + i); with a Comm the best decision is reduced across ranks inside libkp (RCCL all-gather).
-    Returns (choice, stats)."""
-    ch, _, st = plan.argmin(offsets, nodes, base_index=base_index, comm=comm, multi_node=multi_node)
+    allowed (allowed_disruptions): the subsets that exceed a NodePool's allowance are gated out on the device
+    (kp_consolidate_argmin_budgeted; stats["budget_blocked"]). Returns (choice, stats)."""
+    if allowed is None:
+        ch, _, st = plan.argmin(offsets, nodes, base_index=base_index, comm=comm, multi_node=multi_node)
+    else:
+        ch, _, st = plan.argmin(offsets, nodes, base_index=base_index, comm=comm, multi_node=multi_node, allowed=allowed)
     return ch, st

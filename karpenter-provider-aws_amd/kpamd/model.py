@@ -47,6 +47,17 @@ class InstanceType:
 
 
 @dataclass
+class Budget:
+    """One entry of NodePool spec.disruption.budgets (R:pkg/apis/crds/karpenter.sh_nodepools.yaml:95-135): nodes is
+    "p%" or an integer string, reasons a list out of Underutilized / Empty / Drifted (None: every reason), schedule a
+    five-field cron expression or @macro (UTC) that opens a window of duration_s seconds (both or neither)."""
+    nodes: str
+    reasons: Optional[List[str]] = None
+    schedule: Optional[str] = None
+    duration_s: Optional[int] = None
+
+
+@dataclass
 class NodePool:
     name: str
     weight: int = 0
@@ -56,6 +67,7 @@ class NodePool:
     taints: List[Tuple[str, str, str]] = field(default_factory=list)  # (key, value, effect)
     limits: Dict[str, int] = field(default_factory=dict)
     daemon_requests: Dict[str, int] = field(default_factory=dict)
+    budgets: Optional[List[Budget]] = None  # None: not modelled (unlimited); the API server's default is [Budget("10%")]
 
 
 @dataclass
