@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define KP_ABI_VERSION 12
+#define KP_ABI_VERSION 13
 
 enum kp_status {
   KP_OK = 0,
@@ -425,7 +425,10 @@ int32_t kp_ctx_create(const kp_options* opts, kp_ctx** out);
 /* ABI v12: test and measurement overrides of the library's kernel and path choices. Every field 0 (the state a context
  * is created in) is the production choice; no environment variable changes a path (a stray variable in the
  * controller's environment cannot pick another kernel). Cross-check tests and benchmarks set them per context,
- * between calls (not while a call on the context runs). */
+ * between calls (not while a call on the context runs). ABI v13 appends sim_slots and general_launch, which shrink a
+ * launch so that small inputs reach the states a full-size sweep runs in (a wave reusing its slot across subsets, a
+ * general-path launch reusing a dirty arena). Both are read from the context by each simulate / argmin call, not when
+ * the plan was prepared: setting them takes effect on the next call on any existing plan. */
 typedef struct kp_overrides {
   int32_t fast_lane;           /* 0 auto (the run-length-commit variant where most queue neighbours share their shape),
                                   1 the plain variant, 2 the run-length-commit variant */
@@ -441,6 +444,10 @@ typedef struct kp_overrides {
   int32_t feasibility_temporal;/* 0: cheapest-price rows as non-temporal stores; 1: temporal stores */
   int32_t timing;              /* 1: solve_kernel phase probes (kp_solve_stats phase_cycles / fast_cycles) */
   int32_t host_timing;         /* 1: host compile / general-path phases on stderr */
+  int32_t sim_slots;           /* ABI v13. 0: the batched sweep's grid by CU count; n > 0: at most ceil(n / 4) workgroups
+                                  (4 wave slots each), never more than the production grid */
+  int32_t general_launch;      /* ABI v13. 0: general-path simulations per launch by free memory (at most 4096);
+                                  n > 0: at most n per launch */
 } kp_overrides;
 int32_t kp_ctx_set_overrides(kp_ctx* ctx, const kp_overrides* ov); /* NULL: back to all 0 */
 int32_t kp_ctx_get_overrides(const kp_ctx* ctx, kp_overrides* out);
@@ -807,7 +814,10 @@ int32_t kp_simulate_batch(kp_ctx* ctx, const kp_cluster* cluster, const uint32_t
  * a simulation can queue in its pod list) and runs the subsets' Solves batched, one workgroup each; a subset that
  * would remove every owner of an inverse anti-affinity term (and every subset of a cluster whose superset compile is
  * unsupported, or with kp_overrides.general_batch = 1) is compiled on its own. stats (general path): phase_cycles[0] simulations
- * batched, phase_cycles[1] simulations compiled per subset, phase_cycles[2] batched solve_kernel launches. */
+ * batched, phase_cycles[1] simulations compiled per subset, phase_cycles[2] batched solve_kernel launches. stats
+ * (batched sweep, ABI v13; computed by the host): phase_cycles[1] wave slots launched (each wave runs subsets slot,
+ * slot + slots, ...), phase_cycles[2] the most subsets any wave ran, ceil(simulated / slots); a budgeted call counts the
+ * admissible subsets only (both 0 when every subset is blocked). */
 typedef struct kp_cluster_plan kp_cluster_plan;
 int32_t kp_cluster_prepare(kp_ctx* ctx, const kp_cluster* cluster, kp_cluster_plan** out);
 int32_t kp_cluster_simulate(kp_cluster_plan* plan, const uint32_t* offsets, const uint32_t* nodes, uint32_t n_subsets,

@@ -4756,6 +4756,7 @@ struct kp_cluster_plan {
   vector<std::map<string, string>> general_labels;
   bool gb_tried = false;
   uint32_t general_batched = 0;           // simulations of the last general batch that ran batched
+  uint64_t sim_waves[2] = {0, 0};         // the last batched sweep: wave slots launched, most subsets any wave ran
   std::unique_ptr<Compiled> cp;
   DevBuf buf;                       // resident snapshot
   DevBuf scratch;                   // per-wave state, grown on demand
@@ -6022,6 +6023,8 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
   const size_t budget = std::max<size_t>((free_b + held_b) / 8, (size_t)1 << 30);
   size_t per_launch = std::max<size_t>(1, std::min<size_t>(4096, budget / gb.stride));
   if (idx.size() > per_launch && idx.size() < 2 * per_launch) per_launch = (idx.size() + 1) / 2;  // two even launches
+  // kp_overrides.general_launch (read now, not when the plan was prepared): small batches reach the reused arenas
+  if (ctx->ov.general_launch > 0) per_launch = std::min<size_t>(per_launch, (size_t)ctx->ov.general_launch);
   // longest simulations first (queue length: pending + the candidates' pods): they start on the first CUs instead
   // of trailing the launch
   vector<int> order(idx);
@@ -6510,8 +6513,12 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
   if (lds_wg > 160 * 1024) return fail(KP_E_UNSUPPORTED, "simulation LDS %zu B per workgroup (cluster or subsets too large)", lds_wg);
   const int wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds_wg));
   int blocks = std::min<int>((int)((n_subsets + SIM_WAVES - 1) / SIM_WAVES), plan->n_cu * wg_per_cu);
+  // kp_overrides.sim_slots (read now, not when the plan was prepared): fewer waves, so each runs many subsets
+  if (ctx->ov.sim_slots > 0) blocks = std::min(blocks, (ctx->ov.sim_slots + SIM_WAVES - 1) / SIM_WAVES);
   blocks = std::max(blocks, 1);
   const int slots = blocks * SIM_WAVES;
+  plan->sim_waves[0] = (uint64_t)slots;
+  plan->sim_waves[1] = (n_subsets + (uint32_t)slots - 1) / (uint32_t)slots;
   a.n_slots = slots;
   a.n_subsets = (int32_t)n_subsets;
   // per-wave scratch
@@ -6596,6 +6603,8 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
     bg->blocked = n_subsets - n_live;
     blocks = std::max(1, std::min<int>((int)((n_live + SIM_WAVES - 1) / SIM_WAVES), blocks));
     a.n_slots = blocks * SIM_WAVES;  // (the scratch above holds the ungated grid's slots: at least as many)
+    plan->sim_waves[0] = n_live ? (uint64_t)a.n_slots : 0;  // (no live subset: nothing is launched)
+    plan->sim_waves[1] = (n_live + (uint32_t)a.n_slots - 1) / (uint32_t)a.n_slots;
     HIPCHK(hipEventRecord(ctx->ev0, st));
     if (n_live) HIPCHK(launch_sim_gated(a, g.live, (int)n_live, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
     HIPCHK(hipEventRecord(ctx->ev1, st));
@@ -6671,6 +6680,9 @@ static int32_t SimulateImpl(kp_cluster_plan* plan, kp_cancel* cancel, const uint
       stats->phase_cycles[1] = kst[4];
       stats->phase_cycles[2] = kst[6];
       for (int k = 0; k < 8; k++) stats->attempt_cycles[k] = plan->general_phase[k];  // (timing diagnostics)
+    } else {  // batched sweep: wave slots launched, most subsets any wave ran
+      stats->phase_cycles[1] = plan->sim_waves[0];
+      stats->phase_cycles[2] = plan->sim_waves[1];
     }
     stats->prepare_ms = plan->prepare_ms;
     stats->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -6931,6 +6943,9 @@ static int32_t ArgminImpl(kp_cluster_plan* plan, kp_comm* comm, kp_cancel* cance
       stats->phase_cycles[1] = kst[4];
       stats->phase_cycles[2] = kst[6];
       for (int k = 0; k < 8; k++) stats->attempt_cycles[k] = plan->general_phase[k];  // (timing diagnostics)
+    } else {  // batched sweep: wave slots launched, most subsets any wave ran
+      stats->phase_cycles[1] = plan->sim_waves[0];
+      stats->phase_cycles[2] = plan->sim_waves[1];
     }
     stats->prepare_ms = plan->prepare_ms;
     stats->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

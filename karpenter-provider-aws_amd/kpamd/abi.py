@@ -200,11 +200,13 @@ class Options(C.Structure):
 
 
 class Overrides(C.Structure):
-    """kp_overrides (ABI v12): test / measurement overrides of kernel and path choices; all 0 = production."""
+    """kp_overrides (ABI v12; sim_slots and general_launch ABI v13, both read at simulate time): test / measurement
+    overrides of kernel and path choices; all 0 = production."""
     _fields_ = [("fast_lane", C.c_int32), ("sort_capacity", C.c_int32), ("chunk_capacity", C.c_int32),
                 ("template_table", C.c_int32), ("table_shard_min", C.c_uint64), ("general_batch", C.c_int32),
                 ("feasibility_kernel", C.c_int32), ("feasibility_blocks", C.c_int32),
-                ("feasibility_temporal", C.c_int32), ("timing", C.c_int32), ("host_timing", C.c_int32)]
+                ("feasibility_temporal", C.c_int32), ("timing", C.c_int32), ("host_timing", C.c_int32),
+                ("sim_slots", C.c_int32), ("general_launch", C.c_int32)]
 
 
 class EC2Info(C.Structure):

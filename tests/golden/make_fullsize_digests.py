@@ -20,8 +20,13 @@
                   and 200 random subsets of 2..20 candidates (synth.consolidation_subsets seed 5), every decision field
   general-10000   the general path at config 4's size: the 10,000-node spread cluster, the 100 prefixes and 200
                   random subsets of 2..100 candidates (seed 6), every decision field (4 oracle processes, ~4 minutes)
+  sweep-chunk0-sample  (its own file, sweep_chunk0_sample.json) the bench's own sweep: the oracle's record for every
+                  256th subset of chunk 0 of the config-4 10k-node 1M-subset sweep (disruption.sweep_subsets(cl.candidates,
+                  1_000_000, 0, 1): 65,536 subsets, 256 records), for tests/test_sweep_parity.py; 247 s and 263 s of oracle
+                  time on one thread in two runs, the two files identical (the name alone on the command line
+                  writes that file and leaves fullsize_digests.json as it is)
 
-Run from the repo root: python tests/golden/make_fullsize_digests.py [name ...]  (all: about 8 minutes); names given
+Run from the repo root: python tests/golden/make_fullsize_digests.py [name ...]  (all: about 12 minutes); names given
 regenerate only those entries.
 """
 import hashlib
@@ -36,6 +41,8 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "karpenter-provider-aws_amd"))
 
 OUT = os.path.join(HERE, "fullsize_digests.json")
+SWEEP_SAMPLE = os.path.join(HERE, "sweep_chunk0_sample.json")
+SWEEP_SAMPLE_STRIDE = 256
 
 
 def solve_digest(res):
@@ -64,6 +71,15 @@ def config4_subsets(cl):
 def sim_record(r):
     return [int(r["decision"]), int(r["nodepool"]), float(r["candidate_price"]).hex(), float(r["replacement_price"]).hex(),
             float(r["savings"]).hex(), int(r["n_options"]), int(r["n_pods"])]
+
+
+def sweep_sample_subsets(cl, n_subsets=1_000_000, stride=SWEEP_SAMPLE_STRIDE):
+    """(indices, subsets): every stride-th subset of chunk 0 of the config-4 sweep."""
+    from kpamd import disruption
+    offs, nodes, base = disruption.sweep_subsets(cl.candidates, n_subsets, 0, 1)
+    assert base == 0
+    idx = list(range(0, len(offs) - 1, stride))
+    return idx, [[int(x) for x in nodes[offs[i]:offs[i + 1]]] for i in idx]
 
 
 def general_subsets(cl):
@@ -139,6 +155,16 @@ def main():
             recs[i::4] = o
         out["general-10000"] = {"prefixes": recs[:len(pre)], "random": recs[len(pre):]}
         print("general-10000", len(recs), f"{time.time() - t:.1f}s", flush=True)
+    if not only or "sweep-chunk0-sample" in only:
+        t = time.time()
+        cl = synth.config4(cat, n_nodes=10_000, seed=4)
+        idx, subs = sweep_sample_subsets(cl)
+        res, _ = pyoracle.simulate_batch(cl, subs)
+        json.dump({"n_subsets": 1_000_000, "chunk": 0, "stride": SWEEP_SAMPLE_STRIDE, "indices": idx,
+                   "records": [sim_record(r) for r in res]}, open(SWEEP_SAMPLE, "w"), indent=0)
+        print("sweep-chunk0-sample", len(res), f"{time.time() - t:.1f}s", flush=True)
+        if only == {"sweep-chunk0-sample"}:
+            return
     if only and "config4-10000" not in only:
         json.dump(out, open(OUT, "w"), indent=0)
         return

@@ -170,3 +170,38 @@ def test_general_invalid_subsets(ctx, catalog, bad, msg):
         assert len(res) == 3
     finally:
         plan.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bad,msg", [("twice", "twice"), ("range", "node 9999")])
+def test_general_invalid_subsets_on_several_threads(ctx, catalog, bad, msg):
+    """The same check on several host threads (one per 128 subsets: 520 subsets run four): bad subsets at index 100
+    (the first thread's range) and 400 (the last one's); the error names subset 100 whichever thread finishes first, and
+    the plan stays usable."""
+    import numpy as np
+    import kpamd
+    from kpamd import synth
+    cl = synth.spread_cluster(catalog, 40)
+    cands = [int(c) for c in cl.candidates]
+    n = len(cands)
+    subs = [[cands[i % n], cands[(i + 7) % n], cands[(i + 19) % n]] for i in range(520)]
+    assert all(len(set(s)) == 3 for s in subs)
+    if bad == "twice":
+        subs[100] = [cands[0], cands[1], cands[0]]
+        subs[400] = [cands[2], cands[2]]
+    else:
+        subs[100] = [cands[0], 9999]
+        subs[400] = [9998]
+    offs = np.zeros(len(subs) + 1, dtype=np.uint32)
+    offs[1:] = np.cumsum([len(x) for x in subs])
+    flat = np.concatenate([np.asarray(x, dtype=np.uint32) for x in subs])
+    plan = kpamd.ClusterPlan(ctx, cl)
+    try:
+        with pytest.raises(kpamd.KPError) as e:
+            plan.simulate_csr(offs, flat)
+        assert e.value.code == kpamd.abi.KP_E_INVAL
+        assert msg in str(e.value) and "subset 100:" in str(e.value), str(e.value)
+        res, _ = plan.simulate(subs[:3])
+        assert len(res) == 3
+    finally:
+        plan.close()

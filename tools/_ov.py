@@ -1,4 +1,4 @@
-"""Tools only: the diagnostic environment variables of earlier rounds mapped onto kp_overrides (ABI v12). libkp itself
+"""Tools only: the diagnostic environment variables of earlier rounds mapped onto kp_overrides (ABI v12; the two launch-size knobs ABI v13). libkp itself
 reads no environment variable; a tool calls apply(ctx) after creating its context."""
 import os
 
@@ -8,7 +8,8 @@ ENV = {"KP_TIMING": ("timing", lambda v: 1), "KP_HOST_TIMING": ("host_timing", l
        "KP_NO_TFEAS": ("template_table", lambda v: 1), "KP_GENERAL_BATCH": ("general_batch", lambda v: 1 if v == "0" else 0),
        "KP_FEAS_GLOBAL": ("feasibility_kernel", lambda v: 1), "KP_FEAS_ONE_ROW": ("feasibility_kernel", lambda v: 2),
        "KP_FEAS_BLOCKS": ("feasibility_blocks", int), "KP_FEAS_TEMPORAL": ("feasibility_temporal", lambda v: 1),
-       "KP_TFEAS_SHARD_MIN": ("table_shard_min", lambda v: max(1, int(v)))}
+       "KP_TFEAS_SHARD_MIN": ("table_shard_min", lambda v: max(1, int(v))),
+       "KP_SIM_SLOTS": ("sim_slots", int), "KP_GENERAL_LAUNCH": ("general_launch", int)}
 
 
 def apply(ctx, env=None):
