@@ -612,7 +612,10 @@ int32_t kp_filter_compatible_available(kp_ctx* ctx, const kp_catalog* cat, const
                                        kp_solve_stats* stats);
 
 /* Same split into prepare (compile + upload the rows, resident) and run (one launch; copy-out only into
- * non-NULL buffers) so many runs — or a benchmark — reuse resident inputs. */
+ * non-NULL buffers) so many runs — or a benchmark — reuse resident inputs. stats (filter runs; computed by the
+ * host): phase_cycles[0] the kernel the run launched: 1 feasibility_kernel (per type), 2 feasibility_bits_kernel,
+ * 3 feasibility_quad_kernel with a copy wave (price rows), 4 feasibility_quad_kernel with every wave evaluating
+ * (mask only, compact); 0 when there were no rows and nothing was launched. */
 typedef struct kp_filter_plan kp_filter_plan;
 int32_t kp_filter_prepare(kp_ctx* ctx, const kp_catalog* cat, const kp_feasibility_query* queries, uint32_t n_queries,
                           int32_t with_cheapest, kp_filter_plan** out);

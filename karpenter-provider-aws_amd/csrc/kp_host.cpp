@@ -4239,6 +4239,9 @@ int32_t kp_filter_run(kp_filter_plan* plan, uint64_t* out_mask, double* out_chea
     memset(stats, 0, sizeof *stats);
     stats->device_ms = ms;
     stats->attempts = (uint64_t)n * plan->T;  // (row, type) pairs evaluated
+    // the kernel launch_feasibility chose (kp_abi.h): 1 per-type, 2 bits, 3 quad with copy wave, 4 quad all-eval
+    const FeasArgs& fa = plan->fa;
+    stats->phase_cycles[0] = !n ? 0 : !fa.bits ? 1 : (fa.T > 1024 || fa.one_row) ? 2 : fa.out_cheapest ? 3 : 4;
     stats->prepare_ms = plan->prepare_ms;
     stats->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }

@@ -414,6 +414,7 @@ class FilterPlan:
         self.T = len(catalog.instance_types)
         self.n = len(queries)
         mode = 2 if cheapest == "compact" else (1 if cheapest else 0)
+        self.mode = mode
         arena = Arena()
         qs = arena.arr(abi.FeasibilityQuery, [abi.FeasibilityQuery(arena.requirements(r), arena.resources(q))
                                               for r, q in queries])
@@ -422,7 +423,8 @@ class FilterPlan:
         self.h = h
 
     def run(self, read=False):
-        """One launch; read=True copies (kept bool[Q,T], cheapest f64[Q,T]) back, else results stay resident."""
+        """One launch; read=True copies (kept bool[Q,T], cheapest f64[Q,T]) back, else results stay resident. A plan
+        without price rows (mask only, compact) gives cheapest = None."""
         st = abi.SolveStats()
         lib = self.ctx.lib
         if not read:
@@ -430,11 +432,14 @@ class FilterPlan:
             return stats_dict(st)
         tiles = (self.T + 63) // 64
         mask = np.zeros(max(1, self.n * tiles), dtype=np.uint64)
-        cheapest = np.zeros(max(1, self.n * self.T), dtype=np.float64)
+        cheapest = np.zeros(max(1, self.n * self.T), dtype=np.float64) if self.mode == 1 else None
         _check(lib, lib.kp_filter_run(self.h, mask.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                      cheapest.ctypes.data_as(C.POINTER(C.c_double)), C.byref(st)))
+                                      cheapest.ctypes.data_as(C.POINTER(C.c_double)) if self.mode == 1 else None,
+                                      C.byref(st)))
         bits = np.unpackbits(mask[:self.n * tiles].view(np.uint8), bitorder="little").reshape(self.n, tiles * 64)
-        return bits[:, :self.T].astype(bool), cheapest[:self.n * self.T].reshape(self.n, self.T), stats_dict(st)
+        if cheapest is not None:
+            cheapest = cheapest[:self.n * self.T].reshape(self.n, self.T)
+        return bits[:, :self.T].astype(bool), cheapest, stats_dict(st)
 
     def run_compact(self, read=True):
         """kp_filter_run_compact: (kept bool[Q,T], classes uint64[Q], stats); read=False: stats only."""

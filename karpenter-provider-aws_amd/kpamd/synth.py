@@ -719,7 +719,7 @@ def distinct_queries(catalog, n, seed=8):
         if rng.random() < 0.15:
             reqs.append((K + "instance-generation", "Gt", [str(int(rng.integers(2, 7)))]))
         if rng.random() < 0.1 and fams:
-            reqs.append((K + "instance-family", "In", sorted(rng.choice(fams, size=int(rng.integers(2, 16)), replace=False).tolist())))
+            reqs.append((K + "instance-family", "In", sorted(rng.choice(fams, size=min(len(fams), int(rng.integers(2, 16))), replace=False).tolist())))
         if rng.random() < 0.1:
             reqs.append((K + "instance-gpu-manufacturer", "DoesNotExist", []))
         res = req_res(int(rng.integers(1, 400)) * 50, int(rng.integers(1, 512)) * 64)

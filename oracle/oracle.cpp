@@ -47,6 +47,7 @@
 #include <regex>
 #include <set>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "kp/kp_abi.h"
@@ -2087,13 +2088,12 @@ void kpo_result_destroy(kpo_result* r) { delete r; }
 
 // CompatibleAvailableFilter (R:filter.go:39-64) for one query; out_kept[t] = 1 when kept.
 // out_cheapest[t] = cheapest compatible available price (+inf when none).
-int32_t kpo_filter_compatible_available(const kp_catalog_desc* cat, const kp_feasibility_query* q, uint8_t* out_kept,
-                                        double* out_cheapest) {
-  auto types = CatalogFromABI(*cat);
+static void FilterCompatibleAvailable(const vector<InstanceType>& types, const kp_feasibility_query* q,
+                                      uint8_t* out_kept, double* out_cheapest) {
   Requirements reqs = FromABI(q->requirements);
   ResourceList requests = FromABI(q->requests);
-  for (size_t t = 0; t < types->size(); t++) {
-    const InstanceType& it = (*types)[t];
+  for (size_t t = 0; t < types.size(); t++) {
+    const InstanceType& it = types[t];
     bool kept = Compatible(reqs, it.reqs, true) && Fits(requests, it.allocatable) && HasCompatibleAvailable(it, reqs);
     out_kept[t] = kept ? 1 : 0;
     if (out_cheapest) {
@@ -2107,6 +2107,34 @@ int32_t kpo_filter_compatible_available(const kp_catalog_desc* cat, const kp_fea
       out_cheapest[t] = p;
     }
   }
+}
+
+int32_t kpo_filter_compatible_available(const kp_catalog_desc* cat, const kp_feasibility_query* q, uint8_t* out_kept,
+                                        double* out_cheapest) {
+  auto types = CatalogFromABI(*cat);
+  FilterCompatibleAvailable(*types, q, out_kept, out_cheapest);
+  return KP_OK;
+}
+
+// The same filter for n queries over one conversion of the catalogue: row i of out_kept / out_cheapest
+// (n × n_types, out_cheapest optional) is what kpo_filter_compatible_available gives for queries[i]. The rows are
+// independent and the catalogue is only read, so up to 16 threads take interleaved rows: a checker over thousands of
+// rows stays in seconds.
+int32_t kpo_filter_compatible_available_batch(const kp_catalog_desc* cat, const kp_feasibility_query* queries,
+                                              uint32_t n, uint8_t* out_kept, double* out_cheapest) {
+  auto types = CatalogFromABI(*cat);
+  const size_t T = types->size();
+  const uint32_t hw = std::max(1u, std::thread::hardware_concurrency());
+  const uint32_t nth = std::max(1u, std::min({16u, hw, n / 8}));
+  auto work = [&](uint32_t first) {
+    for (uint32_t i = first; i < n; i += nth)
+      FilterCompatibleAvailable(*types, &queries[i], out_kept + (size_t)i * T,
+                                out_cheapest ? out_cheapest + (size_t)i * T : nullptr);
+  };
+  vector<std::thread> pool;
+  for (uint32_t j = 1; j < nth; j++) pool.emplace_back(work, j);
+  work(0);
+  for (auto& th : pool) th.join();
   return KP_OK;
 }
 

@@ -40,6 +40,8 @@ def load(path=LIB_PATH):
         "kpo_result_destroy": (None, [C.c_void_p]),
         "kpo_filter_compatible_available": (C.c_int32, [P(abi.CatalogDesc), P(abi.FeasibilityQuery), P(C.c_uint8),
                                                         P(C.c_double)]),
+        "kpo_filter_compatible_available_batch": (C.c_int32, [P(abi.CatalogDesc), P(abi.FeasibilityQuery), C.c_uint32,
+                                                              P(C.c_uint8), P(C.c_double)]),
         "kpo_filter_spot": (C.c_int32, [P(abi.CatalogDesc), P(abi.Requirements), P(C.c_uint8)]),
         "kpo_launch_select": (C.c_int32, [P(abi.CatalogDesc), P(abi.LaunchRequest), P(C.c_char_p), C.c_uint32,
                                           C.c_uint32, P(abi.LaunchResult), P(C.c_uint32), P(C.c_uint32)]),
@@ -92,6 +94,24 @@ def compatible_available_filter(instance_types, requirements, requests):
     lib.kpo_filter_compatible_available(C.byref(desc), C.byref(q), kept.ctypes.data_as(C.POINTER(C.c_uint8)),
                                         cheapest.ctypes.data_as(C.POINTER(C.c_double)))
     return kept[:len(instance_types)].astype(bool), cheapest[:len(instance_types)]
+
+
+def compatible_available_filter_many(instance_types, queries):
+    """compatible_available_filter for every (requirements, requests) of queries over one conversion of the
+    catalogue: (kept bool[Q,T], cheapest f64[Q,T])."""
+    lib = load()
+    arena = abi.Arena()
+    desc = arena.catalog_desc(instance_types)
+    qs = arena.arr(abi.FeasibilityQuery, [abi.FeasibilityQuery(arena.requirements(r), arena.resources(q))
+                                          for r, q in queries])
+    Q, T = len(queries), len(instance_types)
+    kept = np.zeros(max(1, Q * T), dtype=np.uint8)
+    cheapest = np.zeros(max(1, Q * T), dtype=np.float64)
+    rc = lib.kpo_filter_compatible_available_batch(C.byref(desc), qs, Q, kept.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                   cheapest.ctypes.data_as(C.POINTER(C.c_double)))
+    if rc != 0:
+        raise RuntimeError(f"kpo_filter_compatible_available_batch = {rc}")
+    return kept[:Q * T].reshape(Q, T).astype(bool), cheapest[:Q * T].reshape(Q, T)
 
 
 def _filter(fn, instance_types, requirements):

@@ -147,21 +147,17 @@ def test_filter_plan_pod_rows(ctx, catalog):
     kept, cheapest, st = fp.run(read=True)
     fp.close()
     assert st["attempts"] == len(queries) * len(catalog)
-    seen = {}
-    for qi, (reqs, rq) in enumerate(queries):
-        key = int(prob.pod_shape[qi])
-        if key not in seen:
-            seen[key] = pyoracle.compatible_available_filter(catalog, reqs, rq)
-        want_k, want_c = seen[key]
-        assert (kept[qi] == want_k).all(), f"row {qi}"
-        np.testing.assert_array_equal(cheapest[qi][want_k], want_c[want_k])
+    want_k, want_c = pyoracle.compatible_available_filter_many(catalog, queries)  # every row, every type
+    bad = np.nonzero((kept != want_k).any(axis=1))[0]
+    assert len(bad) == 0, f"rows {bad[:8]}"
+    np.testing.assert_array_equal(cheapest, want_c)
 
 
 def test_feasibility_lds_staged_equals_global(ctx, catalog, ov):
     """The bitset kernels (feasibility_quad_kernel, four rows per wave, at this catalogue size; feasibility_bits_kernel,
     kp_overrides.feasibility_kernel 2) == feasibility_kernel (per-type global gathers, feasibility_kernel 1) bit for bit on pairwise-distinct
     rows (the bench's roofline leg: Gt/Lt bounds, NotIn, zones, capacity types; a row count that leaves the last quad
-    partial), and == the oracle on a sample of rows."""
+    partial), and == the batched oracle on every row, masks and prices of every type."""
     import kpamd
     from kpamd import synth
     from oracle import pyoracle
@@ -191,10 +187,10 @@ def test_feasibility_lds_staged_equals_global(ctx, catalog, ov):
     np.testing.assert_array_equal(c1, c2)
     np.testing.assert_array_equal(c1, c3)
     assert k1.any() and not k1.all()
-    for qi in range(0, len(queries), 97):
-        want_k, want_c = pyoracle.compatible_available_filter(catalog, *queries[qi])
-        assert (k1[qi] == want_k).all(), f"row {qi}"
-        np.testing.assert_array_equal(c1[qi][want_k], want_c[want_k])
+    want_k, want_c = pyoracle.compatible_available_filter_many(catalog, queries)
+    bad = np.nonzero((k1 != want_k).any(axis=1))[0]
+    assert len(bad) == 0, f"rows {bad[:8]}"
+    np.testing.assert_array_equal(c1, want_c)
 
 
 @pytest.mark.parametrize("n_pods", [3_000, 12_000])
@@ -205,15 +201,20 @@ def test_config2_burst(ctx, catalog, n_pods):
     check_same(got, want)
 
 
+_COMPACT_ORACLE = {}
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("kernel", [0, 2, 1])
 def test_filter_compact_equals_expanded(ctx, catalog, ov, kernel):
     """KP_FILTER_COMPACT (ABI v11): the mask and each row's compatible offering classes; min over those classes of
     kp_filter_class_prices equals kp_filter_run's cheapest-price rows bit for bit, on every kernel (quad, one-row,
-    per-type), including after an ICE refresh (R:pkg/providers/instance/filter/filter.go:39-64)."""
+    per-type), including after an ICE refresh (R:pkg/providers/instance/filter/filter.go:39-64); and both equal the
+    batched oracle over the catalogue before and after the ICE marks, every row and type."""
     import copy
     import kpamd
     from kpamd import synth
+    from oracle import pyoracle
     ov(feasibility_kernel=kernel)
     queries = synth.distinct_queries(catalog, 1001)
     its = copy.deepcopy(catalog)
@@ -226,6 +227,12 @@ def test_filter_compact_equals_expanded(ctx, catalog, ov, kernel):
         assert (k1 == k2).all()
         c2 = kpamd.FilterPlan.cheapest_from_compact(cls, fc.class_prices())
         np.testing.assert_array_equal(c1, c2)  # every type, its mask bit set or not (kp_abi.h)
+        if step not in _COMPACT_ORACLE:  # the oracle over the catalogue as it stands at this step, once for the kernels
+            _COMPACT_ORACLE[step] = pyoracle.compatible_available_filter_many(its, queries)
+        want_k, want_c = _COMPACT_ORACLE[step]
+        bad = np.nonzero((k1 != want_k).any(axis=1))[0]
+        assert len(bad) == 0, f"step {step}: rows {bad[:8]}"
+        np.testing.assert_array_equal(c1, want_c)
         if step == 0:  # ICE marks: both plans refreshed in place
             cat.update_offerings([(t, "spot", "test-zone-1a", False) for t in range(0, len(catalog), 3)], seqnum=2)
             with pytest.raises(kpamd.KPError):  # the class prices of a stale plan are refused until the refresh
