@@ -915,6 +915,35 @@ int32_t kp_consolidate_argmin_budgeted(kp_cluster_plan* plan, kp_comm* comm, kp_
                                        const uint32_t* nodes, uint32_t n_subsets, uint64_t base_index, int32_t multi_node,
                                        const uint32_t* allowed, uint32_t n_allowed, kp_sim_result* out, kp_choice* best,
                                        uint64_t* n_blocked, kp_solve_stats* stats);
+/* Drift (R:website/content/en/preview/concepts/disruption.md:131-175; upstream disruption/drift.go), additive to ABI
+ * v13. Each CSR subset (Drift passes singletons; larger subsets are legal) is one SimulateScheduling - the simulation
+ * kp_cluster_simulate builds: the queue is the pending pods, the pods of the nodes being deleted and the subset's pods;
+ * every node that is neither in the subset nor being deleted is an existing node; strict reservations, 100 instance
+ * types, the NodePools' remaining limits - run as a whole device Solve: it does not stop at a second NodeClaim, and no
+ * consolidation decision (price, same-type, spot-to-spot) is taken. out[s] is AllNonPendingPodsScheduled with the
+ * uninitialized-node rule (drift_verdict_kernel on the device); *first is the lowest subset index that is admissible and
+ * feasible (-1: none), and *replacements the Solve result of that subset, owned by the caller (kp_result_destroy) and
+ * read with the kp_result_* accessors: kp_result_pod_placements is indexed by the simulation's input order (pending
+ * pods, the deleting nodes' pods in node order, the subset's pods in subset order), a placement <= -2 names existing
+ * node -2 - placement among the nodes neither in the subset nor being deleted, in cluster order. No NodeClaim: the
+ * subset's nodes are simply deleted. *replacements is NULL when *first is -1.
+ * allowed / n_allowed / *n_blocked: the budget rule of kp_cluster_simulate_budgeted (reason Drifted); allowed == NULL:
+ * no budgets. A blocked subset is neither batched nor compiled: blocked = 1, feasible = 0, never *first. Errors,
+ * stale-plan refusal and cancellation (the plan stays usable) are those of kp_cluster_simulate_budgeted. A plan
+ * kp_cluster_prepare made for the batched simulation kernel builds its superset Solve on the first drift call and keeps
+ * it; kp_cluster_simulate on that plan is unchanged. stats: as the general path reports (phase_cycles[0..2]:
+ * simulations batched, simulations compiled per subset, launches). */
+typedef struct kp_drift_result {
+  int32_t feasible;          /* AllNonPendingPodsScheduled; 0 for a budget-blocked subset */
+  uint32_t n_nodeclaims;     /* new NodeClaims of the simulation's Solve (the whole Solve: no early stop) */
+  uint32_t n_pods;           /* pods queued */
+  uint32_t n_unscheduled;    /* non-pending pods in error or on an uninitialized node */
+  int32_t first_unscheduled; /* cluster pod index of the first such pod in queue order, -1: none */
+  uint32_t blocked;          /* 1: not simulated (budget) */
+} kp_drift_result;
+int32_t kp_cluster_drift(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
+                         uint32_t n_subsets, const uint32_t* allowed, uint32_t n_allowed, kp_drift_result* out,
+                         int64_t* first, kp_solve_result** replacements, uint64_t* n_blocked, kp_solve_stats* stats);
 /* The reduction kp_consolidate_argmin applies to the gathered per-rank records (host-only; exposed for callers that
  * reduce over another transport, and for tests): counts are summed, the best record wins. */
 int32_t kp_choice_reduce(const kp_choice* per_rank, uint32_t n, kp_choice* out);

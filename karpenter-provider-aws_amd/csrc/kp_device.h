@@ -450,6 +450,47 @@ struct GateArgs {
 };
 hipError_t launch_budget_gate(const GateArgs& g, hipStream_t s);
 
+// Drift (kp_cluster_drift): the verdict of every simulation of a general-path launch, and the launch's record.
+// DriftOut mirrors kp_drift_result.
+struct DriftOut {
+  int32_t feasible;
+  uint32_t n_nodeclaims, n_pods, n_unscheduled;
+  int32_t first_unscheduled;
+  uint32_t blocked;
+};
+// drift_first_kernel's record of one launch (the host combines the few launches' records)
+struct DriftRec {
+  int64_t first;      // lowest caller-order subset index among the launch's feasible simulations, -1: none
+  int64_t local;      // that simulation's index in the launch, -1
+  uint64_t feasible;  // feasible simulations
+  uint64_t attempts, bytes, pops;  // the Solves' counters, summed
+  int64_t runaway;    // caller-order index of a simulation that exceeded its Queue.Pop bound, -1: none
+  uint64_t cancelled; // simulations that ended on the kp_cancel flag
+};
+#define DRIFT_WAVES 4
+#define DRIFT_FIRST_THREADS 256
+struct DriftArgs {
+  int32_t n;                     // simulations of the launch
+  int32_t Pc;                    // queue positions an arena holds (stride of qpod)
+  int32_t n_existing;            // E: existing positions of the superset Solve
+  int32_t n_super;               // pods of the superset Solve
+  const uint8_t* arenas;         // the launch's arenas
+  size_t stride;                 // bytes per arena
+  size_t off_place, off_stats;   // the Solve's placements [Pc] and stats [KP_SOLVE_STATS] within an arena
+  const int32_t* qpod;           // [n][Pc] superset pod of each queue position
+  const int32_t* qlen;           // [n] pods queued
+  const int32_t* cidx;           // [n] caller-order subset index
+  const uint8_t* pod_kind;       // [n_super] 2 pending, 1 a deleting node's, 0 a node's (per plan)
+  const int32_t* pod_cluster;    // [n_super] cluster pod index (per plan)
+  const uint8_t* pos_uninit;     // [E] 1: the existing position's node is not initialized (per plan)
+  DriftOut* out;                 // [n_subsets] caller order
+  DriftRec* rec;                 // [1] this launch's record
+};
+hipError_t launch_drift_verdict(const DriftArgs& a, hipStream_t s);
+hipError_t launch_drift_first(const DriftArgs& a, hipStream_t s);
+// finalize over every NodeClaim of the launch's first feasible simulation (rec->local), `max_nc` workgroups
+hipError_t launch_finalize_drift(const FinalizeArgs* dev_args, const DriftRec* rec, int max_nc, hipStream_t s);
+
 // kp_consolidate_argmin: per-block partial bests, and the record each rank contributes to the all-gather
 struct ArgmaxPart {
   double savings;

@@ -3804,6 +3804,111 @@ void kp_cancel_destroy(kp_cancel* c) {
   delete c;
 }
 
+// FinalizeScheduling: a NodeClaim holding reservations launches only into them (reservation-id In {held ids}; the held
+// classes are compatible with its requirements, so the intersection is exactly that set)
+static void ApplyHeld(const SolveBase& B, uint64_t held, KReqs& q) {
+  if (!held) return;
+  const Dict& d = B.d;
+  const int k = d.key(kResID);
+  for (int wi = 0; wi < nwords(d, k); wi++) q.vals[kw(d, k, wi)] = 0;
+  for (uint64_t m = held; m; m &= m - 1) {
+    const int bit = B.classes[__builtin_ctzll(m)].rid_bit;
+    q.vals[bit / 64] |= 1ull << (bit % 64);
+  }
+  q.present |= 1ull << k;
+  q.compl_ &= ~(1ull << k);
+}
+
+// A finished Solve's result sections within its arena (kp_solve_run: the plan's buffer; kp_cluster_drift: the winner's
+// arena of a batched launch), their host copies, and the kp_solve_result built from them.
+struct ResultOffs {
+  size_t place, events, nct, ncrq, opts, nrem, nopt, ncr, held;
+};
+struct ArenaResult {
+  vector<int32_t> place, events, nct;
+  vector<int64_t> ncrq;
+  vector<uint32_t> opts, nrem, nopt;
+  vector<KReqs> fin;
+  vector<uint64_t> held;
+};
+static int32_t FetchArenaResult(hipStream_t st, const uint8_t* base, const ResultOffs& o, int Pc, int opt_stride, bool res_mode,
+                                int n_nc, ArenaResult& r) {
+  if (n_nc < 0 || n_nc > Pc) return fail(KP_E_DEVICE, "Solve result: %d NodeClaims for %d pods", n_nc, Pc);
+  const int nn = std::max(n_nc, 1);
+  r.place.resize(Pc), r.events.resize(Pc), r.nct.resize(nn);
+  r.ncrq.resize((size_t)nn * KP_NRES);
+  r.opts.resize((size_t)nn * opt_stride), r.nrem.resize(nn), r.nopt.resize(nn);
+  r.fin.resize(n_nc);
+  r.held.assign(res_mode ? n_nc : 0, 0);
+  HIPCHK(hipMemcpyAsync(r.place.data(), base + o.place, sizeof(int32_t) * Pc, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(r.events.data(), base + o.events, sizeof(int32_t) * Pc, hipMemcpyDeviceToHost, st));
+  if (n_nc) {
+    HIPCHK(hipMemcpyAsync(r.nct.data(), base + o.nct, sizeof(int32_t) * n_nc, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(r.ncrq.data(), base + o.ncrq, sizeof(int64_t) * n_nc * KP_NRES, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(r.opts.data(), base + o.opts, sizeof(uint32_t) * (size_t)n_nc * opt_stride, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(r.nrem.data(), base + o.nrem, sizeof(uint32_t) * n_nc, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(r.nopt.data(), base + o.nopt, sizeof(uint32_t) * n_nc, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(r.fin.data(), base + o.ncr, sizeof(KReqs) * n_nc, hipMemcpyDeviceToHost, st));
+    if (res_mode) HIPCHK(hipMemcpyAsync(r.held.data(), base + o.held, sizeof(uint64_t) * n_nc, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  return KP_OK;
+}
+// stats: the Solve's stats words ([3] NodeClaims, [4] events); P pods. pod_of(p): the result's index of the Solve's pod
+// p; existing_of(pos): the result's index of the existing node at position pos (-1: none). Applies the held
+// reservations and Truncate's minValues check (a NodeClaim whose truncated options break minValues fails its pods).
+extern "C++" template <class PodOf, class ExistingOf>
+static int32_t AssembleResult(const SolveBase& B, const uint64_t* stats, ArenaResult& a, int P, int opt_stride, PodOf pod_of,
+                              ExistingOf existing_of, kp_solve_result& res) {
+  const Dict& d = B.d;
+  const int n_nc = (int)a.fin.size(), n_ev = (int)stats[4];
+  if (n_ev < 0 || n_ev > (int)a.events.size()) return fail(KP_E_DEVICE, "Solve result: %d events", n_ev);
+  for (int i = 0; i < (int)a.held.size(); i++) ApplyHeld(B, a.held[i], a.fin[i]);
+  res.placement.assign(P, -1);
+  res.ncs.resize(n_nc);
+  for (int i = 0; i < n_ev; i++) {
+    const int p = a.events[i];
+    if (p < 0 || p >= P) return fail(KP_E_DEVICE, "Solve result: event %d names pod %d of %d", i, p, P);
+    const int t = a.place[p];
+    if (t >= 0) {
+      if (t >= n_nc) return fail(KP_E_DEVICE, "Solve result: pod %d on NodeClaim %d of %d", p, t, n_nc);
+      res.ncs[t].pods.push_back((uint32_t)pod_of(p));
+      res.placement[pod_of(p)] = t;
+    } else if (t <= -2) {
+      const int e = existing_of(-2 - t);
+      if (e < 0) return fail(KP_E_DEVICE, "Solve result: pod %d on existing position %d", p, -2 - t);
+      res.placement[pod_of(p)] = -2 - e;
+    }
+  }
+  res.nc_cat.resize(n_nc);
+  for (int i = 0; i < n_nc; i++) {
+    if (a.nct[i] < 0 || a.nct[i] >= (int)B.tmpl_catalog.size() || a.nopt[i] > (uint32_t)opt_stride)
+      return fail(KP_E_DEVICE, "Solve result: NodeClaim %d template %d, %u options", i, a.nct[i], a.nopt[i]);
+    auto& nc = res.ncs[i];
+    res.nc_cat[i] = B.tmpl_catalog[a.nct[i]];
+    nc.nodepool = (uint32_t)B.tmpl_nodepool[a.nct[i]];
+    nc.n_remaining = a.nrem[i];
+    memset(&nc.requests, 0, sizeof nc.requests);
+    for (int r = 0; r < KP_NRES; r++) {
+      nc.requests.milli[r] = a.ncrq[(size_t)i * KP_NRES + r];
+      if (nc.requests.milli[r]) nc.requests.present |= 1u << r;
+    }
+    nc.options.assign(a.opts.begin() + (size_t)i * opt_stride, a.opts.begin() + (size_t)i * opt_stride + a.nopt[i]);
+    nc.reqs = DecodeReqs(d, a.fin[i]);
+    // Truncate(reqs, max): minValues must still hold on the truncated options, else the pods fail
+    if (a.fin[i].hmin & a.fin[i].present) {
+      const HostCat& hc = B.cats[B.tmpl_catalog[a.nct[i]]];
+      vector<int> ts(nc.options.begin(), nc.options.end());
+      if (!HostMinValuesOK(d, hc, a.fin[i], ts)) {
+        for (uint32_t p : nc.pods) res.placement[p] = -1;
+        nc.options.clear();
+      }
+    }
+  }
+  res.fin = a.fin;
+  return KP_OK;
+}
+
 // One Solve over resident inputs: restore mutable state, solve_kernel, finalize_kernel, copy results.
 int32_t kp_solve_run(kp_solve_plan* plan, kp_solve_result** out) { return kp_solve_run_cancellable(plan, nullptr, out); }
 
@@ -3818,7 +3923,6 @@ int32_t kp_solve_run_cancellable(kp_solve_plan* plan, kp_cancel* cancel, kp_solv
   // (a token already set: nothing is queued on the stream)
   if (cancel && __atomic_load_n(cancel->flag, __ATOMIC_SEQ_CST)) return fail(KP_E_CANCELED, "cancelled before the run");
   const Compiled& C = *plan->cp;
-  const Dict& d = C.B->d;
   uint8_t* base = (uint8_t*)plan->buf.p;
   const int P = plan->P, Pc = plan->Pc, opt_stride = plan->opt_stride;
   hipStream_t st = ctx->stream;
@@ -3867,86 +3971,17 @@ int32_t kp_solve_run_cancellable(kp_solve_plan* plan, kp_cancel* cancel, kp_solv
   HIPCHK(hipEventRecord(ctx->ev3, st));
 
   auto res = std::make_unique<kp_solve_result>();
-  res->placement.assign(P, -1);
-  const int nn = std::max(n_nc, 1);
-  vector<int32_t> place(Pc), events(Pc), nct(nn);
-  vector<int64_t> ncrq((size_t)nn * KP_NRES);
-  vector<uint32_t> opts((size_t)nn * opt_stride), nrem(nn), nopt(nn);
-  HIPCHK(hipMemcpyAsync(place.data(), base + plan->o_place, sizeof(int32_t) * Pc, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(events.data(), base + plan->o_events, sizeof(int32_t) * Pc, hipMemcpyDeviceToHost, st));
-  if (n_nc) {
-    HIPCHK(hipMemcpyAsync(nct.data(), base + plan->o_nct, sizeof(int32_t) * n_nc, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(ncrq.data(), base + plan->o_ncrq, sizeof(int64_t) * n_nc * KP_NRES, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(opts.data(), base + plan->o_opts, sizeof(uint32_t) * (size_t)n_nc * opt_stride,
-                          hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(nrem.data(), base + plan->o_nrem, sizeof(uint32_t) * n_nc, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(nopt.data(), base + plan->o_nopt, sizeof(uint32_t) * n_nc, hipMemcpyDeviceToHost, st));
-  }
-  vector<KReqs> fin;
-  vector<uint64_t> held;
-  if (n_nc) {
-    fin.resize(n_nc);
-    HIPCHK(hipMemcpyAsync(fin.data(), base + plan->o_ncr, sizeof(KReqs) * n_nc, hipMemcpyDeviceToHost, st));
-    if (a.res_mode) {
-      held.resize(n_nc);
-      HIPCHK(hipMemcpyAsync(held.data(), base + plan->o_held, sizeof(uint64_t) * n_nc, hipMemcpyDeviceToHost, st));
-    }
-  }
-  HIPCHK(hipStreamSynchronize(st));
-  // FinalizeScheduling: a NodeClaim holding reservations launches only into them (reservation-id In {held ids}; the
-  // held classes are compatible with its requirements, so the intersection is exactly that set)
-  for (int i = 0; i < (int)held.size(); i++) {
-    if (!held[i]) continue;
-    const int k = d.key(kResID);
-    KReqs& q = fin[i];
-    for (int wi = 0; wi < nwords(d, k); wi++) q.vals[kw(d, k, wi)] = 0;
-    for (uint64_t m = held[i]; m; m &= m - 1) {
-      const int bit = C.B->classes[__builtin_ctzll(m)].rid_bit;
-      q.vals[bit / 64] |= 1ull << (bit % 64);
-    }
-    q.present |= 1ull << k;
-    q.compl_ &= ~(1ull << k);
-  }
+  ArenaResult ar;
+  const ResultOffs ro{plan->o_place, plan->o_events, plan->o_nct, plan->o_ncrq, plan->o_opts, plan->o_nrem, plan->o_nopt,
+                      plan->o_ncr, plan->o_held};
+  if (int32_t rc = FetchArenaResult(st, base, ro, Pc, opt_stride, a.res_mode != 0, n_nc, ar)) return rc;
   float ms_solve = 0, ms_fin = 0;
   HIPCHK(hipEventElapsedTime(&ms_solve, ctx->ev0, ctx->ev1));
   HIPCHK(hipEventElapsedTime(&ms_fin, ctx->ev2, ctx->ev3));
-
-  res->ncs.resize(n_nc);
-  const int n_ev = (int)stats[4];
-  for (int i = 0; i < n_ev; i++) {
-    const int p = events[i];
-    const int t = place[p];
-    if (t >= 0) {
-      res->ncs[t].pods.push_back((uint32_t)p);
-      res->placement[p] = t;
-    } else if (t <= -2) {
-      res->placement[p] = -2 - C.ex_input[-2 - t];
-    }
-  }
-  res->fin = fin;
-  res->nc_cat.resize(n_nc);
-  for (int i = 0; i < n_nc; i++) {
-    auto& nc = res->ncs[i];
-    res->nc_cat[i] = C.B->tmpl_catalog[nct[i]];
-    nc.nodepool = (uint32_t)C.B->tmpl_nodepool[nct[i]];
-    nc.n_remaining = nrem[i];
-    memset(&nc.requests, 0, sizeof nc.requests);
-    for (int r = 0; r < KP_NRES; r++) {
-      nc.requests.milli[r] = ncrq[(size_t)i * KP_NRES + r];
-      if (nc.requests.milli[r]) nc.requests.present |= 1u << r;
-    }
-    nc.options.assign(opts.begin() + (size_t)i * opt_stride, opts.begin() + (size_t)i * opt_stride + nopt[i]);
-    nc.reqs = DecodeReqs(d, fin[i]);
-    // Truncate(reqs, max): minValues must still hold on the truncated options, else the pods fail
-    if (!fin.empty() && (fin[i].hmin & fin[i].present)) {
-      const HostCat& hc = C.B->cats[C.B->tmpl_catalog[nct[i]]];
-      vector<int> ts(nc.options.begin(), nc.options.end());
-      if (!HostMinValuesOK(d, hc, fin[i], ts)) {
-        for (uint32_t p : nc.pods) res->placement[p] = -1;
-        nc.options.clear();
-      }
-    }
-  }
+  // pods are the batch's own indices; an existing position is the input index of its node
+  if (int32_t rc = AssembleResult(*C.B, stats, ar, P, opt_stride, [](int p) { return p; },
+                                  [&](int pos) { return pos < (int)C.ex_input.size() ? C.ex_input[pos] : -1; }, *res))
+    return rc;
   memset(&res->stats, 0, sizeof res->stats);
   res->stats.device_ms = ms_solve + ms_fin;
   res->stats.solve_kernel_ms = ms_solve;
@@ -4753,7 +4788,11 @@ struct GeneralBatch;
 struct kp_cluster_plan {
   CtxRef ctx;
   std::unique_ptr<OwnedCluster> general;  // set: simulations run as whole Solves (kp_solve on this device)
-  double general_ms = 0;                  // device time of the last general batch (solve + finalize kernels)
+  // a plan of the batched simulation kernel keeps the cluster too: kp_cluster_drift runs whole Solves on any plan (its
+  // superset Solve `gb` is built on the first drift call); kp_cluster_simulate never reads it
+  std::unique_ptr<OwnedCluster> owned;
+  const OwnedCluster* cluster() const { return general ? general.get() : owned.get(); }
+  double general_ms = 0;                 // device time of the last general batch (solve + finalize kernels)
   uint64_t general_phase[8] = {};         // kp_overrides.timing: the batch's solve_kernel phase cycles, summed
   std::shared_ptr<GeneralBatch> gb;       // the general path's superset Solve (batched simulations), once built
   vector<std::map<string, string>> general_labels;
@@ -4935,8 +4974,28 @@ int32_t kp_cluster_prepare(kp_ctx* ctx, const kp_cluster* cl, kp_cluster_plan** 
     }
   }
   if (topo) return PrepareGeneral(ctx, cl, out, t0);
+  for (uint32_t i = 0; i < cl->n_catalogs; i++)
+    if (!cl->catalogs || !cl->catalogs[i]) return fail(KP_E_INVAL, "catalogue %u is null", i);
   std::lock_guard<std::recursive_mutex> lock(ctx->mu);
   HIPCHK(hipSetDevice(ctx->device));
+  // the owned copy kp_cluster_drift compiles its Solves from: it reads the caller's buffers only (null-tolerant, as on
+  // the general path, where it is made before any validation), so it is made on a thread of its own while the snapshot
+  // is compiled, built and uploaded; every return below joins it
+  struct OwnedCopy {
+    std::unique_ptr<OwnedCluster> oc;
+    bool failed = false;  // the copy threw (out of memory): reported after the join, nothing crosses the thread
+    std::thread th;
+    ~OwnedCopy() {
+      if (th.joinable()) th.join();
+    }
+  } owned_copy;
+  owned_copy.th = std::thread([&owned_copy, cl] {
+    try {
+      owned_copy.oc = std::make_unique<OwnedCluster>(cl);
+    } catch (...) {
+      owned_copy.failed = true;
+    }
+  });
   auto plan = std::make_unique<kp_cluster_plan>();
   plan->ctx = ctx;
   plan->cp = std::make_unique<Compiled>();
@@ -5216,6 +5275,9 @@ int32_t kp_cluster_prepare(kp_ctx* ctx, const kp_cluster* cl, kp_cluster_plan** 
   plan->node_flags = node_flags;
   HIPCHK(launch_sim_prep(a, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
+  owned_copy.th.join();
+  if (owned_copy.failed || !owned_copy.oc) return fail(KP_E_NOMEM, "out of host memory copying the cluster");
+  plan->owned = std::move(owned_copy.oc);
   plan->prepare_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   *out = plan.release();
   return KP_OK;
@@ -5492,30 +5554,24 @@ static void GeneralDecide(const kp_cluster& cl, const vector<std::map<string, st
   r.n_options = (uint32_t)kept.size();
 }
 
-// FinalizeScheduling: a NodeClaim holding reservations launches only into them (reservation-id In {held ids})
-static void ApplyHeld(const SolveBase& B, uint64_t held, KReqs& q) {
-  if (!held) return;
-  const Dict& d = B.d;
-  const int k = d.key(kResID);
-  for (int wi = 0; wi < nwords(d, k); wi++) q.vals[kw(d, k, wi)] = 0;
-  for (uint64_t m = held; m; m &= m - 1) {
-    const int bit = B.classes[__builtin_ctzll(m)].rid_bit;
-    q.vals[bit / 64] |= 1ull << (bit % 64);
-  }
-  q.present |= 1ull << k;
-  q.compl_ &= ~(1ull << k);
-}
-
 // One subset's SimulateScheduling as its own Solve: compiled on the host from the subset's inputs (the path for
 // subsets the batch cannot take, and the whole path with KP_GENERAL_BATCH=0).
-static int32_t GeneralSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand, const vector<std::map<string, string>>& labels,
-                             int32_t multi_node, SimOut& r, uint64_t* counters, double* dev_ms, kp_cancel* cancel) {
+struct SimOneSolve {
+  vector<kp_existing_node> ex;  // the Solve's existing nodes: neither in the subset nor being deleted, cluster order
+  vector<int> kind;             // per queued pod (input order): 0 candidate pod, 1 deleting-node pod, 2 pending
+  vector<uint32_t> cluster_pod; // per queued pod: its cluster pod index
+  std::unique_ptr<kp_solve_plan, void (*)(kp_solve_plan*)> sp{nullptr, kp_solve_plan_destroy};
+  std::unique_ptr<kp_solve_result, void (*)(kp_solve_result*)> res{nullptr, kp_result_destroy};
+};
+static int32_t GeneralSolveOne(kp_cluster_plan* plan, const vector<uint32_t>& cand, SimOneSolve& so, uint64_t* counters,
+                               double* dev_ms, kp_cancel* cancel) {
   kp_ctx* ctx = plan->ctx;
-  const kp_cluster& cl = plan->general->cl;
+  const kp_cluster& cl = plan->cluster()->cl;
   const int N = (int)cl.n_nodes;
   vector<char> inS(N, 0);
   for (uint32_t c : cand) inS[c] = 1;
-  vector<kp_existing_node> ex;
+  vector<kp_existing_node>& ex = so.ex;
+  vector<int>& kind = so.kind;
   vector<int> exNode;
   for (int i = 0; i < N; i++)
     if (!inS[i] && !cl.nodes[i].deleting) {
@@ -5523,23 +5579,20 @@ static int32_t GeneralSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand
       exNode.push_back(i);
     }
   vector<kp_pod> pods;
-  vector<int> kind;  // 0 candidate pod, 1 deleting-node pod, 2 pending
+  auto add = [&](uint32_t p, int k) {
+    pods.push_back(cl.pods[p]);
+    kind.push_back(k);
+    so.cluster_pod.push_back(p);
+  };
   for (uint32_t j = 0; j < cl.n_pending; j++) {
     if (cl.pending_pods[j] >= cl.n_pods) return fail(KP_E_INVAL, "pending pod %u", cl.pending_pods[j]);
-    pods.push_back(cl.pods[cl.pending_pods[j]]);
-    kind.push_back(2);
+    add(cl.pending_pods[j], 2);
   }
   for (int i = 0; i < N; i++)
     if (cl.nodes[i].deleting)
-      for (uint32_t j = 0; j < cl.nodes[i].n_pods; j++) {
-        pods.push_back(cl.pods[cl.nodes[i].pods[j]]);
-        kind.push_back(1);
-      }
+      for (uint32_t j = 0; j < cl.nodes[i].n_pods; j++) add(cl.nodes[i].pods[j], 1);
   for (uint32_t c : cand)
-    for (uint32_t j = 0; j < cl.nodes[c].n_pods; j++) {
-      pods.push_back(cl.pods[cl.nodes[c].pods[j]]);
-      kind.push_back(0);
-    }
+    for (uint32_t j = 0; j < cl.nodes[c].n_pods; j++) add(cl.nodes[c].pods[j], 0);
   vector<kp_bound_pod> bound;
   for (size_t e = 0; e < exNode.size(); e++) {
     const kp_cluster_node& n = cl.nodes[exNode[e]];
@@ -5551,7 +5604,6 @@ static int32_t GeneralSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand
                        sh.n_required_anti_affinity, 0});
     }
   }
-  r.n_pods = (uint32_t)pods.size();
   kp_solve_in in;
   memset(&in, 0, sizeof in);
   in.catalogs = cl.catalogs;
@@ -5573,18 +5625,29 @@ static int32_t GeneralSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand
   kp_solve_plan* sp = nullptr;
   int32_t rc = SolvePrepare(ctx, &in, nullptr, &sp);
   if (rc) return rc;
-  std::unique_ptr<kp_solve_plan, void (*)(kp_solve_plan*)> spg(sp, kp_solve_plan_destroy);
+  so.sp.reset(sp);
   kp_solve_result* res = nullptr;
   rc = kp_solve_run_cancellable(sp, cancel, &res);
   if (rc) return rc;
-  std::unique_ptr<kp_solve_result, void (*)(kp_solve_result*)> rg(res, kp_result_destroy);
+  so.res.reset(res);
   counters[0] += res->stats.attempts;
   counters[1] += res->stats.bytes_algorithmic;
   counters[2] += res->stats.pops;
   *dev_ms += res->stats.device_ms;
+  return KP_OK;
+}
+static int32_t GeneralSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand, const vector<std::map<string, string>>& labels,
+                             int32_t multi_node, SimOut& r, uint64_t* counters, double* dev_ms, kp_cancel* cancel) {
+  SimOneSolve so;
+  if (int32_t rc = GeneralSolveOne(plan, cand, so, counters, dev_ms, cancel)) return rc;
+  const kp_cluster& cl = plan->cluster()->cl;
+  const vector<kp_existing_node>& ex = so.ex;
+  const vector<int>& kind = so.kind;
+  const kp_solve_result* res = so.res.get();
+  r.n_pods = (uint32_t)kind.size();
   // AllNonPendingPodsScheduled; a candidate pod on an uninitialized node is an error (deleting-node pods exempt)
   bool all = true;
-  for (size_t p = 0; p < pods.size() && all; p++) {
+  for (size_t p = 0; p < kind.size() && all; p++) {
     const int32_t pl = res->placement[p];
     if (kind[p] == 2) continue;
     if (pl == -1) all = false;
@@ -5592,7 +5655,7 @@ static int32_t GeneralSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand
   }
   const int n_nc = (int)res->ncs.size();
   // (kp_solve_run already applied the held reservations and the minValues truncation check to NodeClaim 0)
-  GeneralDecide(cl, labels, cand, *sp->cp->B, all, n_nc, n_nc ? &res->fin[0] : nullptr, n_nc ? res->nc_cat[0] : 0,
+  GeneralDecide(cl, labels, cand, *so.sp->cp->B, all, n_nc, n_nc ? &res->fin[0] : nullptr, n_nc ? res->nc_cat[0] : 0,
                 n_nc ? res->ncs[0].nodepool : 0, n_nc ? res->ncs[0].options.data() : nullptr,
                 n_nc ? (uint32_t)res->ncs[0].options.size() : 0, multi_node, r);
   return KP_OK;
@@ -5642,6 +5705,8 @@ struct PinnedBuf {
 struct GenSlot {
   DevBuf arenas, args;
   size_t arenas_bytes = 0, args_bytes = 0;
+  DevBuf drift;  // drift launches: the simulations' queue pods, lengths and caller indices, and the launch's record
+  size_t drift_bytes = 0;
   PinnedBuf up, down;
   hipEvent_t done = nullptr, t0 = nullptr, t1 = nullptr;  // results landed; the launch's kernels (timing)
   hipEvent_t uploaded = nullptr;                            // the launch's overlays and arguments on the device
@@ -5694,13 +5759,21 @@ struct GeneralBatch {
   DevBuf pristine;
   GenSlot slot[2];  // two launch slots (GeneralBatchRun)
   CopyStreams cs;
+  // kp_cluster_drift: what drift_verdict_kernel gathers, uploaded once per plan (DriftTables), and the verdicts
+  vector<int32_t> pod_cluster;  // superset pod -> cluster pod index
+  bool min_values = false;      // some template or shape-level carries minValues (drift: the per-subset path)
+  DevBuf drift_tab, drift_out;
+  size_t drift_out_n = 0;
+  const uint8_t* d_pod_kind = nullptr;
+  const int32_t* d_pod_cluster = nullptr;
+  const uint8_t* d_pos_uninit = nullptr;
 };
 
 // The superset Solve of a cluster (kp_cluster_plan: general). KP_E_UNSUPPORTED: the batch cannot take this cluster
 // (the caller keeps the per-subset compile).
 static int32_t GeneralBatchBuild(kp_cluster_plan* plan, std::shared_ptr<GeneralBatch>& out) {
   kp_ctx* ctx = plan->ctx;
-  const kp_cluster& cl = plan->general->cl;
+  const kp_cluster& cl = plan->cluster()->cl;
   const int N = (int)cl.n_nodes;
   PhaseTimer pt;
   auto gb = std::make_shared<GeneralBatch>();
@@ -5713,12 +5786,14 @@ static int32_t GeneralBatchBuild(kp_cluster_plan* plan, std::shared_ptr<GeneralB
     if (cl.pending_pods[j] >= cl.n_pods) return fail(KP_E_INVAL, "pending pod %u", cl.pending_pods[j]);
     pods.push_back(cl.pods[cl.pending_pods[j]]);
     gb->pod_kind.push_back(2);
+    gb->pod_cluster.push_back((int32_t)cl.pending_pods[j]);
   }
   for (int i = 0; i < N; i++)
     if (cl.nodes[i].deleting)
       for (uint32_t j = 0; j < cl.nodes[i].n_pods; j++) {
         pods.push_back(cl.pods[cl.nodes[i].pods[j]]);
         gb->pod_kind.push_back(1);
+        gb->pod_cluster.push_back((int32_t)cl.nodes[i].pods[j]);
       }
   const int n_base = (int)pods.size();
   for (int i = 0; i < N; i++) {
@@ -5734,6 +5809,7 @@ static int32_t GeneralBatchBuild(kp_cluster_plan* plan, std::shared_ptr<GeneralB
       gb->node_pods[i].push_back((int32_t)pods.size());
       pods.push_back(cl.pods[p]);
       gb->pod_kind.push_back(0);
+      gb->pod_cluster.push_back((int32_t)p);
     }
   }
   {  // queue ties broken by pod index would order differently per subset: only distinct (creation, UID) keys
@@ -5804,6 +5880,8 @@ static int32_t GeneralBatchBuild(kp_cluster_plan* plan, std::shared_ptr<GeneralB
     }
   }
   pt.lap("general: tracking");
+  for (const KReqs& q : C.B->tmpl_reqs) gb->min_values |= (q.hmin & q.present) != 0;
+  for (const KReqs& q : C.shape_reqs) gb->min_values |= (q.hmin & q.present) != 0;
   gb->rmask = RequestedResources(C);
   gb->ex_static = ExStatic(C, gb->rmask);
   gb->offers.Build(C.B->d, cl);
@@ -5982,13 +6060,28 @@ static int GeneralPatch(const GeneralBatch& gb, const kp_cluster& cl, const vect
   return 0;
 }
 
+// kp_cluster_drift's state across the launches of one call (GeneralBatchRun in drift mode, DriftSimOne)
+struct DriftRun {
+  vector<DriftOut> host_out;  // caller order: the verdicts taken on the host (subsets compiled on their own) ...
+  vector<char> on_host;       // ... and which entries those are; the rest come from the device array
+  DriftOut* d_out = nullptr;  // [n_subsets] drift_verdict_kernel's verdicts, caller order
+  int64_t first = -1;         // the lowest feasible caller-order subset so far
+  std::unique_ptr<kp_solve_result> res;  // its Solve result
+};
+static int32_t DriftSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand, int s, DriftRun& dr, uint64_t* counters,
+                           double* dev_ms, kp_cancel* cancel);
+static int32_t DriftFetch(kp_cluster_plan* plan, GeneralBatch& gb, const GenSlot& sl, int j, const vector<uint32_t>& cand,
+                          std::unique_ptr<kp_solve_result>& out);
+
 // Runs the batchable subsets `idx` (their candidate lists in cands) as batched Solves; outs[idx[i]] get the decisions.
+// dr (kp_cluster_drift): the Solves run whole (no early stop), and instead of the decisions the launch leaves its
+// verdicts in dr->d_out and one record; the host reads the record and, when it lowers dr->first, the winner's result.
 static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const vector<vector<uint32_t>>& cands,
                                const vector<int>& idx, const vector<std::map<string, string>>& labels, int32_t multi_node,
                                vector<SimOut>& outs, uint64_t* counters, double* dev_ms, double* host_ms,
-                               kp_cancel* cancel, uint64_t* n_launches) {
+                               kp_cancel* cancel, uint64_t* n_launches, DriftRun* dr = nullptr) {
   kp_ctx* ctx = plan->ctx;
-  const kp_cluster& cl = plan->general->cl;
+  const kp_cluster& cl = plan->cluster()->cl;
   const Compiled& C = *gb.C;
   hipStream_t st = ctx->stream;
   // kp_cancel: solve_kernel polls the flag (every ~1,024 pops of each simulation) and the host reads it before each
@@ -6054,6 +6147,12 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
   const size_t u_args = (patch_bytes * per_launch + 255) & ~(size_t)255;
   const size_t u_fargs = u_args + ((sizeof(SolveArgs) * per_launch + 255) & ~(size_t)255);
   const size_t u_end = u_fargs + sizeof(FinalizeArgs) * per_launch;
+  // drift launches: the slot's drift buffer (queue pods [n][Pc], lengths [n], caller indices [n], then the record),
+  // mirrored in the upload buffer behind the arguments
+  const size_t d_qlen = sizeof(int32_t) * (size_t)Pc * per_launch, d_cidx = d_qlen + sizeof(int32_t) * per_launch;
+  const size_t d_rec = (d_cidx + sizeof(int32_t) * per_launch + 255) & ~(size_t)255;
+  const size_t u_drift = (u_end + 255) & ~(size_t)255;
+  const size_t up_need = dr ? u_drift + d_rec : u_end, down_need = dr ? sizeof(DriftRec) : r_end;
 
   // the host decisions of a finished launch (its results in the slot's download buffer)
   auto decide = [&](GenSlot& sl) -> int32_t {
@@ -6126,6 +6225,32 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
     return KP_OK;
   };
 
+  // drift: the launch's record; its first feasible simulation's result when that lowers the call's first
+  auto decide_drift = [&](GenSlot& sl) -> int32_t {
+    HIPCHK(hipEventSynchronize(sl.done));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, sl.t0, sl.t1));
+    *dev_ms += ms;
+    const auto th1 = std::chrono::steady_clock::now();
+    const DriftRec rec = *reinterpret_cast<const DriftRec*>(sl.down.at(0));
+    counters[0] += rec.attempts;
+    counters[1] += rec.bytes;
+    counters[2] += rec.pops;
+    if (rec.runaway >= 0)
+      return fail(KP_E_DEVICE, "solve_kernel exceeded its Queue.Pop bound in simulation %lld: aborted", (long long)rec.runaway);
+    if (rec.cancelled) return fail(KP_E_CANCELED, "drift simulations cancelled (kp_cancel_set)");
+    if (rec.first >= 0 && (dr->first < 0 || rec.first < dr->first)) {
+      if (rec.local < 0 || rec.local >= sl.n || order[sl.b0 + (size_t)rec.local] != rec.first)
+        return fail(KP_E_DEVICE, "drift record: simulation %lld of the launch is not subset %lld", (long long)rec.local,
+                    (long long)rec.first);
+      if (int32_t rc = DriftFetch(plan, gb, sl, (int)rec.local, cands[rec.first], dr->res)) return rc;
+      dr->first = rec.first;
+    }
+    host_ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th1).count();
+    return KP_OK;
+  };
+  auto decide_any = [&](GenSlot& sl) -> int32_t { return dr ? decide_drift(sl) : decide(sl); };
+
   GenSlot* slots = gb.slot;
   for (int k = 0; k < 2; k++)
     if (!slots[k].done) {
@@ -6168,16 +6293,22 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
       ae = sl.args.alloc(args_need);
       sl.args_bytes = ae == hipSuccess ? args_need : 0;
     }
-    if (ae == hipSuccess) ae = sl.up.reserve(u_end);
-    if (ae == hipSuccess) ae = sl.down.reserve(r_end);
+    if (ae == hipSuccess) ae = sl.up.reserve(up_need);
+    if (ae == hipSuccess) ae = sl.down.reserve(down_need);
+    if (ae == hipSuccess && dr && sl.drift_bytes < d_rec + sizeof(DriftRec)) {
+      ae = sl.drift.alloc(d_rec + sizeof(DriftRec));
+      sl.drift_bytes = ae == hipSuccess ? d_rec + sizeof(DriftRec) : 0;
+    }
     if (ae != hipSuccess) {
       (void)hipGetLastError();
       if (pending >= 0) {
-        if (int32_t rc = decide(slots[pending])) return rc;
+        if (int32_t rc = decide_any(slots[pending])) return rc;
         pending = -1;
       }
       for (size_t j = b0; j < idx.size(); j++)
-        if (int32_t rc = GeneralSimOne(plan, cands[order[j]], labels, multi_node, outs[order[j]], counters, dev_ms, cancel)) return rc;
+        if (int32_t rc = dr ? DriftSimOne(plan, cands[order[j]], order[j], *dr, counters, dev_ms, cancel)
+                            : GeneralSimOne(plan, cands[order[j]], labels, multi_node, outs[order[j]], counters, dev_ms, cancel))
+          return rc;
       break;
     }
     uint8_t* arenas = (uint8_t*)sl.arenas.p;
@@ -6203,7 +6334,9 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
       SolveArgs& a = sargs[j];
       BindSolve(a, C, o, sh, ar, (int)queues[j].size(), Pc, gb.rmask, gb.res_mode);
       a.cancel = dcancel;
-      a.stop_nc = 2;  // a second NodeClaim decides the simulation (no-op): the kernel ends its Solve there
+      // a second NodeClaim decides a consolidation simulation (no-op): the kernel ends its Solve there; a drift
+      // simulation is the whole Solve
+      a.stop_nc = dr ? 0 : 2;
       a.ex_reqs_ro = (const uint8_t*)gb.pristine.p + (o.exr - o.common);  // (the arena's copy is written on demand)
       a.ex_ulist = (const int32_t*)(sh + gb.so.exul);
       a.ex_ulist_off = (const int32_t*)(sh + gb.so.exuo);
@@ -6274,66 +6407,106 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
     HIPCHK(hipMemcpy2DAsync(arenas, gb.stride, patches, patch_bytes, patch_bytes, n, hipMemcpyHostToDevice, up));
     HIPCHK(hipMemcpyAsync(dargs, reinterpret_cast<uint8_t*>(sl.up.at(u_args)), sizeof(SolveArgs) * n, hipMemcpyHostToDevice, up));
     HIPCHK(hipMemcpyAsync(dfargs, reinterpret_cast<uint8_t*>(sl.up.at(u_fargs)), sizeof(FinalizeArgs) * n, hipMemcpyHostToDevice, up));
+    DriftArgs da;
+    memset(&da, 0, sizeof da);
+    if (dr) {
+      uint8_t* hd = sl.up.at(u_drift);
+      uint8_t* dd = (uint8_t*)sl.drift.p;
+      int32_t* qpod = reinterpret_cast<int32_t*>(hd);
+      int32_t* qlen = reinterpret_cast<int32_t*>(hd + d_qlen);
+      int32_t* cidx = reinterpret_cast<int32_t*>(hd + d_cidx);
+      for (int j = 0; j < n; j++) {
+        memcpy(qpod + (size_t)j * Pc, queues[j].data(), sizeof(int32_t) * queues[j].size());
+        qlen[j] = (int32_t)queues[j].size();
+        cidx[j] = order[b0 + j];
+      }
+      HIPCHK(hipMemcpyAsync(dd, hd, sizeof(int32_t) * (size_t)Pc * n, hipMemcpyHostToDevice, up));
+      HIPCHK(hipMemcpyAsync(dd + d_qlen, hd + d_qlen, sizeof(int32_t) * n, hipMemcpyHostToDevice, up));
+      HIPCHK(hipMemcpyAsync(dd + d_cidx, hd + d_cidx, sizeof(int32_t) * n, hipMemcpyHostToDevice, up));
+      da.n = n;
+      da.Pc = Pc;
+      da.n_existing = (int32_t)C.ex_input.size();
+      da.n_super = (int32_t)gb.pod_kind.size();
+      da.arenas = arenas;
+      da.stride = gb.stride;
+      da.off_place = o.place;
+      da.off_stats = o.stats;
+      da.qpod = reinterpret_cast<const int32_t*>(dd);
+      da.qlen = reinterpret_cast<const int32_t*>(dd + d_qlen);
+      da.cidx = reinterpret_cast<const int32_t*>(dd + d_cidx);
+      da.pod_kind = gb.d_pod_kind;
+      da.pod_cluster = gb.d_pod_cluster;
+      da.pos_uninit = gb.d_pos_uninit;
+      da.out = dr->d_out;
+      da.rec = reinterpret_cast<DriftRec*>(dd + d_rec);
+    }
     HIPCHK(hipEventRecord(sl.uploaded, up));
     hipStream_t ks = gb.cs.k[launch_no & 1];  // (the slot's kernel stream)
     HIPCHK(launch_batch_init(bi, n, ks));
     HIPCHK(hipStreamWaitEvent(ks, sl.uploaded, 0));
     HIPCHK(hipEventRecord(sl.t0, ks));
     HIPCHK(launch_solve_batch(sargs[0], dargs, n, dyn, ks));
-    HIPCHK(launch_finalize_batch(fargs[0], dfargs, n, ks));
+    if (dr) {
+      // the verdicts, the launch's record, then every NodeClaim of its first feasible simulation finalized while the
+      // arena is resident (at most as many as the launch's longest queue, its first simulation's)
+      HIPCHK(launch_drift_verdict(da, ks));
+      HIPCHK(launch_drift_first(da, ks));
+      HIPCHK(launch_finalize_drift(dfargs, da.rec, std::max(1, std::min(Pc, (int)len[order[b0]])), ks));
+    } else {
+      HIPCHK(launch_finalize_batch(fargs[0], dfargs, n, ks));
+    }
     HIPCHK(hipEventRecord(sl.t1, ks));
     // downloads on their own stream once the kernels are done (the next launch's kernels need not wait for them)
     HIPCHK(hipStreamWaitEvent(dn, sl.t1, 0));
-    auto down = [&](size_t roff, size_t off, size_t width) {
-      return hipMemcpy2DAsync(reinterpret_cast<uint8_t*>(sl.down.at(roff)), width, arenas + off, gb.stride, width, n, hipMemcpyDeviceToHost, dn);
-    };
-    HIPCHK(down(r_stats, o.stats, sizeof(uint64_t) * KP_SOLVE_STATS));
-    HIPCHK(down(r_place, o.place, sizeof(int32_t) * Pc));
-    HIPCHK(down(r_nct, o.nct, sizeof(int32_t)));
-    HIPCHK(down(r_nopt, o.nopt, sizeof(uint32_t)));
-    HIPCHK(down(r_opts, o.opts, sizeof(uint32_t) * gb.opt_stride));
-    HIPCHK(down(r_fin, o.ncr, sizeof(KReqs)));
-    if (gb.res_mode) HIPCHK(down(r_held, o.held, sizeof(uint64_t)));
+    if (dr) {  // drift launches download the record only (the verdicts: one copy at the end of the call)
+      HIPCHK(hipMemcpyAsync(sl.down.at(0), da.rec, sizeof(DriftRec), hipMemcpyDeviceToHost, dn));
+    } else {
+      auto down = [&](size_t roff, size_t off, size_t width) {
+        return hipMemcpy2DAsync(reinterpret_cast<uint8_t*>(sl.down.at(roff)), width, arenas + off, gb.stride, width, n, hipMemcpyDeviceToHost, dn);
+      };
+      HIPCHK(down(r_stats, o.stats, sizeof(uint64_t) * KP_SOLVE_STATS));
+      HIPCHK(down(r_place, o.place, sizeof(int32_t) * Pc));
+      HIPCHK(down(r_nct, o.nct, sizeof(int32_t)));
+      HIPCHK(down(r_nopt, o.nopt, sizeof(uint32_t)));
+      HIPCHK(down(r_opts, o.opts, sizeof(uint32_t) * gb.opt_stride));
+      HIPCHK(down(r_fin, o.ncr, sizeof(KReqs)));
+      if (gb.res_mode) HIPCHK(down(r_held, o.held, sizeof(uint64_t)));
+    }
     HIPCHK(hipEventRecord(sl.done, dn));
     sl.n = n;
     sl.b0 = b0;
     // the previous launch's decisions while this one runs
     if (pending >= 0) {
-      if (int32_t rc = decide(slots[pending])) return rc;
+      if (int32_t rc = decide_any(slots[pending])) return rc;
     }
     pending = launch_no & 1;
     ++*n_launches;
   }
   if (pending >= 0) {
-    if (int32_t rc = decide(slots[pending])) return rc;
+    if (int32_t rc = decide_any(slots[pending])) return rc;
   }
   return KP_OK;
 }
 
-static int32_t GeneralSimLocked(kp_cluster_plan* plan, const uint32_t* offsets, const uint32_t* nodes,
-                                uint32_t n_subsets, int32_t multi_node, SimArgs& a, kp_cancel* cancel, BudgetGate* bg) {
+// The subsets of a general-path call, checked and split: cands[s] the members of subset s; batched / single the
+// subsets the superset Solve takes / those compiled on their own; the budget-blocked ones are in neither (bg->blocked
+// counts them). Builds the plan's superset Solve when it has none (again after an offering refresh of its catalogues).
+// drift: a superset compile carrying minValues is not batched (Truncate's minValues check needs the options on the host).
+static int32_t GeneralPartition(kp_cluster_plan* plan, const uint32_t* offsets, const uint32_t* nodes, uint32_t n_subsets,
+                                BudgetGate* bg, bool drift, vector<vector<uint32_t>>& cands_out, vector<int>& batched,
+                                vector<int>& single, vector<char>* blocked_out = nullptr) {
   kp_ctx* ctx = plan->ctx;
-  const kp_cluster& cl = plan->general->cl;
+  const kp_cluster& cl = plan->cluster()->cl;
   const int N = (int)cl.n_nodes;
-  if (int32_t rc = CatalogsAlive(plan->general->alive)) return rc;
+  if (int32_t rc = CatalogsAlive(plan->cluster()->alive)) return rc;
   if (offsets[0] != 0) return fail(KP_E_INVAL, "offsets[0] != 0");
   if (offsets[n_subsets] && !nodes) return fail(KP_E_INVAL, "null nodes");
-  using clk = std::chrono::steady_clock;
-  const auto t0 = clk::now();
-  vector<std::map<string, string>>& labels = plan->general_labels;  // the nodes' labels (NodeCandidatePrice), once
-  if ((int)labels.size() != N) {
-    labels.assign(N, {});
-    for (int i = 0; i < N; i++)
-      for (uint32_t j = 0; j < cl.nodes[i].node.n_labels; j++) {
-        const kp_label& l = cl.nodes[i].node.labels[j];
-        labels[i][Normalize(l.key ? l.key : "")] = l.value ? l.value : "";
-      }
-  }
   for (uint32_t s = 0; s < n_subsets; s++)
     if (offsets[s + 1] < offsets[s]) return fail(KP_E_INVAL, "offsets not monotone at %u", s);
   // the subsets' candidate lists, checked on up to 16 threads (each with its own membership marks); the error reported
   // is the first subset's, as the serial check would report it
-  vector<vector<uint32_t>> cands(n_subsets);
+  vector<vector<uint32_t>>& cands = cands_out;
+  cands.assign(n_subsets, {});
   std::atomic<int64_t> bad_s{INT64_MAX};
   vector<vector<char>> inS(kMaxHostThreads);
   ParallelFor((int)n_subsets, [&](int s_lo, int s_hi, int t) {
@@ -6392,13 +6565,6 @@ static int32_t GeneralSimLocked(kp_cluster_plan* plan, const uint32_t* offsets, 
     if (rc && rc != KP_E_UNSUPPORTED) return rc;
     if (rc) plan->gb.reset();
   }
-  const double t_setup = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-  vector<SimOut> outs(n_subsets);
-  memset(outs.data(), 0, sizeof(SimOut) * outs.size());
-  uint64_t counters[3] = {0, 0, 0}, n_launches = 0;
-  memset(plan->general_phase, 0, sizeof plan->general_phase);
-  double dev_ms = 0, host_ms[2] = {0, 0};  // the batch's host work: overlays + arguments, decisions
-  vector<int> batched, single;
   vector<char> batchable(n_subsets, 0), blocked(n_subsets, 0);
   ParallelFor((int)n_subsets, [&](int s_lo, int s_hi, int) {
     vector<uint32_t> per_pool(bg ? plan->n_pools : 0);
@@ -6409,7 +6575,7 @@ static int32_t GeneralSimLocked(kp_cluster_plan* plan, const uint32_t* offsets, 
           if (++per_pool[plan->node_pool[c]] > bg->allowed[plan->node_pool[c]]) blocked[s] = 1;
         if (blocked[s]) continue;  // neither batched nor compiled: the zero no-op
       }
-      bool ok = batch_on && plan->gb;
+      bool ok = batch_on && plan->gb && !(drift && plan->gb->min_values);
       if (ok && plan->gb->C->G) {  // an inverse anti-affinity group would vanish: the per-subset compile
         const Compiled& C = *plan->gb->C;
         std::map<int, int> inv;
@@ -6427,6 +6593,35 @@ static int32_t GeneralSimLocked(kp_cluster_plan* plan, const uint32_t* offsets, 
     }
     (batchable[s] ? batched : single).push_back((int)s);
   }
+  if (blocked_out) blocked_out->swap(blocked);
+  return KP_OK;
+}
+
+static int32_t GeneralSimLocked(kp_cluster_plan* plan, const uint32_t* offsets, const uint32_t* nodes,
+                                uint32_t n_subsets, int32_t multi_node, SimArgs& a, kp_cancel* cancel, BudgetGate* bg) {
+  kp_ctx* ctx = plan->ctx;
+  const kp_cluster& cl = plan->general->cl;
+  const int N = (int)cl.n_nodes;
+  using clk = std::chrono::steady_clock;
+  const auto t0 = clk::now();
+  vector<std::map<string, string>>& labels = plan->general_labels;  // the nodes' labels (NodeCandidatePrice), once
+  if ((int)labels.size() != N) {
+    labels.assign(N, {});
+    for (int i = 0; i < N; i++)
+      for (uint32_t j = 0; j < cl.nodes[i].node.n_labels; j++) {
+        const kp_label& l = cl.nodes[i].node.labels[j];
+        labels[i][Normalize(l.key ? l.key : "")] = l.value ? l.value : "";
+      }
+  }
+  vector<vector<uint32_t>> cands;
+  vector<int> batched, single;
+  if (int32_t rc = GeneralPartition(plan, offsets, nodes, n_subsets, bg, false, cands, batched, single)) return rc;
+  const double t_setup = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+  vector<SimOut> outs(n_subsets);
+  memset(outs.data(), 0, sizeof(SimOut) * outs.size());
+  uint64_t counters[3] = {0, 0, 0}, n_launches = 0;
+  memset(plan->general_phase, 0, sizeof plan->general_phase);
+  double dev_ms = 0, host_ms[2] = {0, 0};  // the batch's host work: overlays + arguments, decisions
   const auto t1 = clk::now();
   if (!batched.empty()) {
     const int32_t rc = GeneralBatchRun(plan, *plan->gb, cands, batched, labels, multi_node, outs, counters, &dev_ms, host_ms,
@@ -6463,6 +6658,209 @@ static int32_t GeneralSimLocked(kp_cluster_plan* plan, const uint32_t* offsets, 
             "device %.2f) single %.2f ms\n", n_subsets, batched.size(), single.size(), t_setup, t_batch, host_ms[0],
             host_ms[1], dev_ms, t_single);
   return KP_OK;
+}
+
+// ---- Drift (kp_cluster_drift) ----------------------------------------------------------------------------------
+// Each subset is the simulation above run as a whole Solve; what comes back is AllNonPendingPodsScheduled per subset
+// and the Solve result of the first feasible one. Batched subsets: solve_kernel (stop_nc 0), drift_verdict_kernel,
+// drift_first_kernel and finalize_drift_kernel per launch (GeneralBatchRun); the others: their own Solve, the verdict
+// taken on the host from the result kp_solve_run has already copied back.
+
+// drift_verdict_kernel's gathers, uploaded once per superset Solve: pod kind and cluster pod per superset pod, the
+// "not initialized" byte per existing position
+static int32_t DriftTables(kp_ctx* ctx, GeneralBatch& gb, const kp_cluster& cl) {
+  if (gb.drift_tab.p) return KP_OK;
+  const size_t P = gb.pod_kind.size(), E = gb.pos_node.size();
+  const size_t o_cl = (P + 255) & ~(size_t)255, o_un = (o_cl + sizeof(int32_t) * P + 255) & ~(size_t)255;
+  vector<uint8_t> h(o_un + std::max<size_t>(E, 1), 0);
+  if (P) memcpy(h.data(), gb.pod_kind.data(), P);
+  if (P) memcpy(h.data() + o_cl, gb.pod_cluster.data(), sizeof(int32_t) * P);
+  for (size_t e = 0; e < E; e++) h[o_un + e] = cl.nodes[gb.pos_node[e]].node.initialized ? 0 : 1;
+  HIPCHK(gb.drift_tab.alloc(h.size()));
+  HIPCHK(hipMemcpyAsync(gb.drift_tab.p, h.data(), h.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const uint8_t* d = (const uint8_t*)gb.drift_tab.p;
+  gb.d_pod_kind = d;
+  gb.d_pod_cluster = reinterpret_cast<const int32_t*>(d + o_cl);
+  gb.d_pos_uninit = d + o_un;
+  return KP_OK;
+}
+
+// The Solve result of simulation j of a finished drift launch, read from its arena (still resident: the slot is reused
+// by the launch after the next, which is not queued yet): what kp_solve_run copies back, in kp_cluster_drift's indices
+// (pods in the simulation's input order, existing nodes among those neither in the subset nor being deleted).
+static int32_t DriftFetch(kp_cluster_plan* plan, GeneralBatch& gb, const GenSlot& sl, int j, const vector<uint32_t>& cand,
+                          std::unique_ptr<kp_solve_result>& out) {
+  kp_ctx* ctx = plan->ctx;
+  const kp_cluster& cl = plan->cluster()->cl;
+  const Compiled& C = *gb.C;
+  const SolveOffs& o = gb.o;
+  const int Pc = gb.Pc, opt_stride = gb.opt_stride;
+  const uint8_t* ar = (const uint8_t*)sl.arenas.p + gb.stride * (size_t)j;
+  const vector<int32_t>& q = sl.queues[j];
+  hipStream_t st = ctx->stream;
+  uint64_t stats[KP_SOLVE_STATS];
+  HIPCHK(hipMemcpyAsync(stats, ar + o.stats, sizeof stats, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const int P = (int)q.size();
+  if (P > Pc) return fail(KP_E_DEVICE, "drift result: %d pods in an arena of %d", P, Pc);
+  ArenaResult a;
+  const ResultOffs ro{o.place, o.events, o.nct, o.ncrq, o.opts, o.nrem, o.nopt, o.ncr, o.held};
+  if (int32_t rc = FetchArenaResult(st, ar, ro, Pc, opt_stride, gb.res_mode != 0, (int)stats[3], a)) return rc;
+  // queue position -> input index: the base pods are the superset's first pods in input order already; the subset's
+  // follow in subset order
+  const int n_base = (int)gb.base_pods.size(), N = (int)cl.n_nodes;
+  std::unordered_map<int32_t, int32_t> sub_in;
+  int32_t next = n_base;
+  for (uint32_t c : cand)
+    for (int32_t sp : gb.node_pods[c]) sub_in[sp] = next++;
+  vector<int32_t> in_of(P);
+  for (int p = 0; p < P; p++) in_of[p] = q[p] < n_base ? q[p] : sub_in.at(q[p]);
+  // existing position -> index among the nodes neither in the subset nor being deleted, cluster order
+  vector<int32_t> ex_rank(N, -1);
+  {
+    vector<char> inS(N, 0);
+    for (uint32_t c : cand) inS[c] = 1;
+    int32_t r = 0;
+    for (int i = 0; i < N; i++)
+      if (!inS[i] && !cl.nodes[i].deleting) ex_rank[i] = r++;
+  }
+  auto res = std::make_unique<kp_solve_result>();
+  if (int32_t rc = AssembleResult(*C.B, stats, a, P, opt_stride, [&](int p) { return in_of[p]; },
+                                  [&](int pos) { return pos < (int)gb.pos_node.size() ? ex_rank[gb.pos_node[pos]] : -1; }, *res))
+    return rc;
+  memset(&res->stats, 0, sizeof res->stats);
+  res->stats.attempts = stats[0];
+  res->stats.bytes_algorithmic = stats[1];
+  res->stats.pops = stats[2];
+  res->stats.scanned = stats[5];
+  res->stats.cursor_starts = stats[6];
+  res->stats.prepare_ms = plan->prepare_ms;
+  out = std::move(res);
+  return KP_OK;
+}
+
+// A subset compiled on its own: its Solve, the verdict from the result on the host (queue order: the Solve's own)
+static int32_t DriftSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand, int s, DriftRun& dr, uint64_t* counters,
+                           double* dev_ms, kp_cancel* cancel) {
+  SimOneSolve so;
+  if (int32_t rc = GeneralSolveOne(plan, cand, so, counters, dev_ms, cancel)) return rc;
+  const kp_solve_result* res = so.res.get();
+  DriftOut o;
+  memset(&o, 0, sizeof o);
+  o.n_nodeclaims = (uint32_t)res->ncs.size();
+  o.n_pods = (uint32_t)so.kind.size();
+  o.first_unscheduled = -1;
+  for (int32_t p : so.sp->cp->queue) {
+    const int32_t pl = res->placement[p];
+    const int kind = so.kind[p];
+    if (kind == 2) continue;
+    if (pl == -1 || (kind == 0 && pl <= -2 && !so.ex[(size_t)(-2 - pl)].initialized)) {
+      if (o.n_unscheduled++ == 0) o.first_unscheduled = (int32_t)so.cluster_pod[p];
+    }
+  }
+  o.feasible = o.n_unscheduled == 0 ? 1 : 0;
+  dr.host_out[s] = o;
+  dr.on_host[s] = 1;
+  if (o.feasible && (dr.first < 0 || s < dr.first)) {
+    dr.first = s;
+    dr.res.reset(so.res.release());
+  }
+  return KP_OK;
+}
+
+static int32_t DriftLocked(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
+                           uint32_t n_subsets, BudgetGate* bg, kp_drift_result* out, int64_t* first,
+                           kp_solve_result** replacements, kp_solve_stats* stats) {
+  kp_ctx* ctx = plan->ctx;
+  if (cancel && __atomic_load_n(cancel->flag, __ATOMIC_SEQ_CST)) return fail(KP_E_CANCELED, "cancelled before the simulations");
+  if (!plan->cluster()) return fail(KP_E_INVAL, "the plan holds no cluster");
+  if (!plan->general) {  // a plan of the batched simulation kernel: its stale-plan refusal, as kp_cluster_simulate's
+    if (int32_t rc = CatalogsAlive(plan->cp->B->alive)) return rc;
+    if (SeqnumsOf(plan->cp->B->catalogs) != plan->cp->B->seqnums)
+      return fail(KP_E_INVAL, "stale plan: a catalogue's seqnum changed since it was prepared (kp_cluster_refresh)");
+  }
+  using clk = std::chrono::steady_clock;
+  const auto t0 = clk::now();
+  vector<vector<uint32_t>> cands;
+  vector<int> batched, single;
+  vector<char> blocked;
+  if (int32_t rc = GeneralPartition(plan, offsets, nodes, n_subsets, bg, true, cands, batched, single, &blocked)) return rc;
+  // (the general path's per-call diagnostics: a drift call reports no solve_kernel phase cycles, and leaves none of an
+  // earlier simulate call behind)
+  memset(plan->general_phase, 0, sizeof plan->general_phase);
+  plan->general_ms = 0;
+  plan->general_batched = 0;
+  DriftRun dr;
+  dr.host_out.assign(n_subsets, DriftOut{});
+  dr.on_host.assign(n_subsets, 0);
+  uint64_t counters[3] = {0, 0, 0}, n_launches = 0;
+  double dev_ms = 0, host_ms[2] = {0, 0};
+  if (!batched.empty()) {
+    GeneralBatch& gb = *plan->gb;
+    if (int32_t rc = DriftTables(ctx, gb, plan->cluster()->cl)) return rc;
+    if (gb.drift_out_n < n_subsets) {
+      HIPCHK(gb.drift_out.alloc(sizeof(DriftOut) * n_subsets));
+      gb.drift_out_n = n_subsets;
+    }
+    dr.d_out = (DriftOut*)gb.drift_out.p;
+    static const vector<std::map<string, string>> no_labels;
+    vector<SimOut> no_outs;
+    if (int32_t rc = GeneralBatchRun(plan, gb, cands, batched, no_labels, 0, no_outs, counters, &dev_ms, host_ms, cancel,
+                                     &n_launches, &dr))
+      return rc;
+    // the verdicts of every launch: one copy (the launches have drained: their records were read)
+    vector<DriftOut> dev(n_subsets);
+    HIPCHK(hipMemcpyAsync(dev.data(), dr.d_out, sizeof(DriftOut) * n_subsets, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (int s : batched)
+      if (!dr.on_host[s]) dr.host_out[s] = dev[s];
+  }
+  for (int s : single)
+    if (int32_t rc = DriftSimOne(plan, cands[s], s, dr, counters, &dev_ms, cancel)) return rc;
+  for (uint32_t s = 0; s < n_subsets; s++)
+    if (blocked[s]) dr.host_out[s].blocked = 1, dr.host_out[s].first_unscheduled = -1;
+  static_assert(sizeof(DriftOut) == sizeof(kp_drift_result), "DriftOut mirrors kp_drift_result");
+  if (out && n_subsets) memcpy(out, dr.host_out.data(), sizeof(DriftOut) * n_subsets);
+  *first = dr.first;
+  if (replacements) *replacements = dr.res.release();
+  if (stats) {
+    stats->device_ms = dev_ms;
+    stats->solve_kernel_ms = dev_ms;
+    stats->attempts = counters[0];
+    stats->bytes_algorithmic = counters[1];
+    stats->pops = counters[2];
+    stats->phase_cycles[0] = batched.size();
+    stats->phase_cycles[1] = single.size();
+    stats->phase_cycles[2] = n_launches;
+    stats->prepare_ms = plan->prepare_ms;
+    stats->host_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+  }
+  if (ctx->ov.host_timing)
+    fprintf(stderr, "[kp drift] %u sims (%zu batched, %zu single, %llu launches): overlays %.2f records %.2f device %.2f ms\n",
+            n_subsets, batched.size(), single.size(), (unsigned long long)n_launches, host_ms[0], host_ms[1], dev_ms);
+  return KP_OK;
+}
+
+int32_t kp_cluster_drift(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
+                         uint32_t n_subsets, const uint32_t* allowed, uint32_t n_allowed, kp_drift_result* out,
+                         int64_t* first, kp_solve_result** replacements, uint64_t* n_blocked, kp_solve_stats* stats) {
+  if (n_blocked) *n_blocked = 0;
+  if (first) *first = -1;
+  if (replacements) *replacements = nullptr;
+  if (!plan || !first || (n_subsets && !offsets)) return fail(KP_E_INVAL, "null argument");
+  if (cancel && cancel->ctx.p != plan->ctx.p) return fail(KP_E_INVAL, "the cancel token belongs to another context");
+  kp_ctx* ctx = plan->ctx;
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  HIPCHK(hipSetDevice(ctx->device));
+  if (stats) memset(stats, 0, sizeof *stats);
+  BudgetGate bg{allowed, n_allowed};
+  if (allowed)
+    if (int32_t rc = CheckBudget(plan, &bg)) return rc;
+  if (n_subsets == 0) return KP_OK;
+  const int32_t rc = DriftLocked(plan, cancel, offsets, nodes, n_subsets, allowed ? &bg : nullptr, out, first, replacements, stats);
+  if (!rc && n_blocked) *n_blocked = bg.blocked;
+  return rc;
 }
 
 static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, const uint32_t* nodes, uint32_t n_subsets,

@@ -4379,16 +4379,29 @@ hipError_t launch_tmpl_feas(const TfeasArgs& a, hipStream_t s) {
 #define FIN_MAX_T 4096
 // BATCH: workgroup y finalizes NodeClaim 0 of simulation y (batch[y]) when that Solve made exactly one NodeClaim (the
 // only case a consolidation decision reads options from), its count read from the Solve's stats on the device.
+__device__ __forceinline__ void finalize_nodeclaim(const FinalizeArgs& a, const int nc);
 template <bool BATCH>
 __global__ __launch_bounds__(FIN_THREADS) void finalize_kernel(FinalizeArgs a0, const FinalizeArgs* __restrict__ batch) {
+  const FinalizeArgs& a = BATCH ? batch[blockIdx.x] : a0;
+  if (BATCH && a.solve_stats[3] != 1) return;
+  finalize_nodeclaim(a, BATCH ? 0 : blockIdx.x);
+}
+// Drift: workgroup x finalizes NodeClaim x of the launch's first feasible simulation (drift_first_kernel's record, read
+// on the device: the host has not seen it yet), every NodeClaim that Solve made.
+__global__ __launch_bounds__(FIN_THREADS) void finalize_drift_kernel(const FinalizeArgs* __restrict__ batch,
+                                                                     const DriftRec* __restrict__ rec) {
+  const int64_t j = rec->local;
+  if (j < 0) return;
+  const FinalizeArgs& a = batch[j];
+  if ((uint64_t)blockIdx.x >= a.solve_stats[3]) return;
+  finalize_nodeclaim(a, blockIdx.x);
+}
+__device__ __forceinline__ void finalize_nodeclaim(const FinalizeArgs& a, const int nc) {
   __shared__ DevDict D;
   __shared__ uint64_t s_cls;
   __shared__ uint64_t s_key[FIN_MAX_T];
   __shared__ uint32_t s_idx[FIN_MAX_T];
   __shared__ uint32_t s_cnt;
-  const FinalizeArgs& a = BATCH ? batch[blockIdx.x] : a0;
-  if (BATCH && a.solve_stats[3] != 1) return;
-  const int nc = BATCH ? 0 : blockIdx.x;
   block_copy(D, a.dict);
   if (threadIdx.x == 0) s_cnt = 0;
   __syncthreads();
@@ -5634,6 +5647,11 @@ hipError_t launch_finalize(const FinalizeArgs& a, hipStream_t s) {
 hipError_t launch_finalize_batch(const FinalizeArgs& a0, const FinalizeArgs* dev_args, int n, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL((finalize_kernel<true>), dim3(n), dim3(FIN_THREADS), 0, s, a0, dev_args);
+  return hipGetLastError();
+}
+hipError_t launch_finalize_drift(const FinalizeArgs* dev_args, const DriftRec* rec, int max_nc, hipStream_t s) {
+  if (max_nc <= 0) return hipSuccess;
+  hipLaunchKernelGGL(finalize_drift_kernel, dim3(max_nc), dim3(FIN_THREADS), 0, s, dev_args, rec);
   return hipGetLastError();
 }
 // Batched Solves' arenas: every arena [y] = base + y * stride gets the shared pristine block copied to `dst_off` (but

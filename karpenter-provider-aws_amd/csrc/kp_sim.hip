@@ -962,3 +962,124 @@ hipError_t launch_budget_gate(const GateArgs& g, hipStream_t s) {
   hipLaunchKernelGGL(gate_scatter_kernel, dim3(nb), dim3(64), 0, s, g);
   return hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------------
+// Drift (kp_cluster_drift): every simulation of a general-path launch is a whole Solve (no early stop); what the host
+// needs of it is AllNonPendingPodsScheduled, not its placements. drift_verdict_kernel reduces each simulation's
+// placements to one 24-byte DriftOut, drift_first_kernel the launch's verdicts to one record (the lowest caller-order
+// subset index among the feasible ones, the Solves' counters); the launch then downloads verdicts only. Both run
+// behind solve_kernel in the launch's stream. Plain (vector) stores, no global atomics: each output has one writer.
+// ------------------------------------------------------------------------------------------------
+// One wave per simulation; the lanes stride over its queue positions: placement, the pod's kind (2 pending, 1 a
+// deleting node's, 0 a candidate's) and, for a candidate pod on an existing node, that position's "not initialized"
+// bit. The ballot of a 64-position chunk gives the count and - its lowest bit in the first chunk that has one - the
+// first failing position.
+__global__ __launch_bounds__(DRIFT_WAVES * 64) void drift_verdict_kernel(DriftArgs a) {
+  const int lane = LANE;
+  const int j = blockIdx.x * DRIFT_WAVES + (threadIdx.x >> 6);
+  if (j >= a.n) return;  // (wave-uniform)
+  const uint8_t* ar = a.arenas + a.stride * (size_t)j;
+  const int32_t* place = reinterpret_cast<const int32_t*>(ar + a.off_place);
+  const uint64_t* st = reinterpret_cast<const uint64_t*>(ar + a.off_stats);
+  const int32_t* qp = a.qpod + (size_t)j * a.Pc;
+  const int n = max(0, min(a.qlen[j], a.Pc));
+  uint32_t n_bad = 0;
+  int first = -1;
+  for (int p0 = 0; p0 < n; p0 += 64) {
+    const int p = p0 + lane;
+    bool bad = false;
+    if (p < n) {
+      const int32_t pl = place[p];
+      const uint32_t sp = (uint32_t)qp[p];
+      const uint32_t kind = sp < (uint32_t)a.n_super ? a.pod_kind[sp] : 2u;
+      if (kind != 2u) {
+        if (pl == -1) {
+          bad = true;
+        } else if (kind == 0u && pl <= -2) {  // SimulateScheduling's UninitializedNodeError (deleting nodes' pods exempt)
+          const uint32_t pos = (uint32_t)(-(pl + 2));
+          bad = pos < (uint32_t)a.n_existing && a.pos_uninit[pos] != 0;
+        }
+      }
+    }
+    const uint64_t m = __ballot(bad);
+    if (m) {
+      n_bad += (uint32_t)__builtin_popcountll(m);
+      if (first < 0) first = p0 + __builtin_ctzll(m);
+    }
+  }
+  if (lane == 0) {
+    DriftOut o;
+    o.feasible = n_bad == 0 ? 1 : 0;
+    o.n_nodeclaims = (uint32_t)st[3];
+    o.n_pods = (uint32_t)n;
+    o.n_unscheduled = n_bad;
+    o.first_unscheduled = -1;
+    if (first >= 0) {
+      const uint32_t sp = (uint32_t)qp[first];
+      if (sp < (uint32_t)a.n_super) o.first_unscheduled = a.pod_cluster[sp];
+    }
+    o.blocked = 0;
+    a.out[a.cidx[j]] = o;
+  }
+}
+// One block per launch: the lowest caller-order index among the launch's feasible simulations (the launches are ordered
+// longest-first, so this is not the launch-local index) with its launch-local index, and the sums of the Solves'
+// counters. Every thread folds its simulations in index order and the tree is fixed, so the record does not depend on
+// arrival order.
+__global__ __launch_bounds__(DRIFT_FIRST_THREADS) void drift_first_kernel(DriftArgs a) {
+  __shared__ int64_t s_first[DRIFT_FIRST_THREADS], s_run[DRIFT_FIRST_THREADS];
+  __shared__ uint64_t s_sum[5][DRIFT_FIRST_THREADS];
+  const int tid = threadIdx.x;
+  int64_t first = INT64_MAX, run = INT64_MAX;  // first: caller index << 32 | launch-local index
+  uint64_t sum[5] = {0, 0, 0, 0, 0};           // feasible, attempts, bytes, pops, cancelled
+  for (int j = tid; j < a.n; j += DRIFT_FIRST_THREADS) {
+    const uint64_t* st = reinterpret_cast<const uint64_t*>(a.arenas + a.stride * (size_t)j + a.off_stats);
+    const int64_t c = a.cidx[j];
+    const bool bad = st[7] != 0 || st[46] != 0;  // a Solve that did not finish has no verdict
+    if (st[7] != 0 && c < run) run = c;
+    sum[4] += st[46] != 0 ? 1 : 0;
+    sum[1] += st[0];
+    sum[2] += st[1];
+    sum[3] += st[2];
+    if (!bad && a.out[c].feasible) {
+      sum[0]++;
+      const int64_t key = (c << 32) | (int64_t)j;
+      if (key < first) first = key;
+    }
+  }
+  s_first[tid] = first;
+  s_run[tid] = run;
+  for (int k = 0; k < 5; k++) s_sum[k][tid] = sum[k];
+  __syncthreads();
+  for (int w = DRIFT_FIRST_THREADS / 2; w > 0; w >>= 1) {
+    if (tid < w) {
+      if (s_first[tid + w] < s_first[tid]) s_first[tid] = s_first[tid + w];
+      if (s_run[tid + w] < s_run[tid]) s_run[tid] = s_run[tid + w];
+      for (int k = 0; k < 5; k++) s_sum[k][tid] += s_sum[k][tid + w];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    DriftRec r;
+    const bool any = s_first[0] != INT64_MAX;
+    r.first = any ? (s_first[0] >> 32) : -1;
+    r.local = any ? (s_first[0] & 0xFFFFFFFFll) : -1;
+    r.feasible = s_sum[0][0];
+    r.attempts = s_sum[1][0];
+    r.bytes = s_sum[2][0];
+    r.pops = s_sum[3][0];
+    r.runaway = s_run[0] != INT64_MAX ? s_run[0] : -1;
+    r.cancelled = s_sum[4][0];
+    *a.rec = r;
+  }
+}
+hipError_t launch_drift_verdict(const DriftArgs& a, hipStream_t s) {
+  if (a.n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(drift_verdict_kernel, dim3((a.n + DRIFT_WAVES - 1) / DRIFT_WAVES), dim3(DRIFT_WAVES * 64), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_drift_first(const DriftArgs& a, hipStream_t s) {
+  if (a.n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(drift_first_kernel, dim3(1), dim3(DRIFT_FIRST_THREADS), 0, s, a);
+  return hipGetLastError();
+}

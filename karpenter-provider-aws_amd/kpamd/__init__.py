@@ -5,6 +5,7 @@ The surfaces mirror the reference's plugin/operator interface for the path:
   Scheduler(...).solve(pods)                  <- upstream scheduling.Scheduler.Solve
   compatible_available_filter(...)            <- R:pkg/providers/instance/filter/filter.go:39-64
   ClusterPlan(...).simulate(subsets)          <- upstream disruption computeConsolidation / SimulateScheduling
+  ClusterPlan(...).drift(subsets)             <- upstream disruption Drift: SimulateScheduling, the whole Solve
 Everything computes behind the C ABI on the GPU; a missing libkp.so or HIP device raises.
 """
 import ctypes as C
@@ -117,6 +118,9 @@ def load_lib(path=None):
                                                        C.c_uint32, C.c_uint64, C.c_int32, P(C.c_uint32), C.c_uint32,
                                                        P(abi.SimResult), P(abi.Choice), P(C.c_uint64),
                                                        P(abi.SolveStats)]),
+        "kp_cluster_drift": (C.c_int32, [C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32), C.c_uint32, P(C.c_uint32),
+                                         C.c_uint32, P(abi.DriftResult), P(C.c_int64), P(C.c_void_p), P(C.c_uint64),
+                                         P(abi.SolveStats)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name, None)
@@ -677,6 +681,36 @@ class ClusterPlan:
                                                                              C.byref(blocked), C.byref(st)))
             sd = dict(stats_dict(st), budget_blocked=int(blocked.value))
         return choice_dict(ch), (out[:n] if out is not None else None), sd
+
+    def drift(self, subsets, allowed=None, cancel=None, read_all=False):
+        """kp_cluster_drift: every subset (list of node indices; Drift passes singletons) simulated as a whole Solve.
+        Returns {"first": the lowest admissible feasible subset index or -1, "replacements": read_result of that subset's
+        Solve (placements in the simulation's input order: pending, deleting nodes' pods, the subset's pods) or None,
+        "results": the per-subset kp_drift_result dicts when read_all, "blocked": subsets the budget blocked (allowed:
+        allowed disruptions per NodePool, reason Drifted), "stats"}."""
+        lib = self.ctx.lib
+        arena = Arena()
+        offs, flat = abi.subsets_csr(arena, subsets)
+        n = len(subsets)
+        out = (abi.DriftResult * max(1, n))() if read_all else None
+        first, res, blocked, st = C.c_int64(-1), C.c_void_p(), C.c_uint64(0), abi.SolveStats()
+        keep, ap, na = self._allowed(allowed) if allowed is not None else (None, None, 0)
+        _check(lib, lib.kp_cluster_drift(self.h, cancel.h if cancel is not None else None, offs, flat, n, ap, na, out,
+                                         C.byref(first), C.byref(res), C.byref(blocked), C.byref(st)))
+        try:
+            repl = None
+            if res.value:
+                cl, w = self.cluster, subsets[first.value]
+                n_pods = len(cl.pending) + sum(len(x.pods) for x in cl.nodes if x.deleting) + sum(len(cl.nodes[c].pods) for c in w)
+                repl = read_result(lib, res, n_pods)
+        finally:
+            if res.value:
+                lib.kp_result_destroy(res)
+        results = None
+        if read_all:
+            results = [{f: int(getattr(out[i], f)) for f, _ in abi.DriftResult._fields_} for i in range(n)]
+        return {"first": int(first.value), "replacements": repl, "results": results, "blocked": int(blocked.value),
+                "stats": stats_dict(st)}
 
     def close(self):
         if self.h:

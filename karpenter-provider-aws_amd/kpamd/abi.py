@@ -273,6 +273,12 @@ class SimResult(C.Structure):
                 ("n_pods", C.c_uint32)]
 
 
+class DriftResult(C.Structure):
+    """kp_drift_result: AllNonPendingPodsScheduled of one drift simulation (kp_cluster_drift)."""
+    _fields_ = [("feasible", C.c_int32), ("n_nodeclaims", C.c_uint32), ("n_pods", C.c_uint32),
+                ("n_unscheduled", C.c_uint32), ("first_unscheduled", C.c_int32), ("blocked", C.c_uint32)]
+
+
 class Choice(C.Structure):
     """kp_choice: the sweep's best decision over all ranks (kp_consolidate_argmin / kp_choice_reduce)."""
     _fields_ = [("subset", C.c_int64), ("counts", C.c_uint64 * 3), ("overflowed", C.c_uint64), ("result", SimResult)]

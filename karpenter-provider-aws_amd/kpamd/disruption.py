@@ -18,8 +18,13 @@ CS3 and R:website/content/en/preview/concepts/disruption.md:89-128):
   Emptiness.compute_command                 the candidates without reschedulable pods, deleted in one command
   candidate_order(cluster)                  the consolidatable nodes in disruption-cost order (ReschedulingCost of
                                             default-priority pods = their count; ties by node name)
-  Controller.compute_command(cluster, plan) one disruption pass over the methods the e2e consolidation suite
-                                            exercises, in upstream order (Emptiness, MultiNodeConsolidation,
+  Drift.compute_command(cluster, plan)      the drifted nodes (ClusterNode.drifted, oldest first): the empty ones
+                                            deleted in one command, else the first whose SimulateScheduling
+                                            reschedules every non-pending pod, replaced by that Solve's NodeClaims
+                                            (R:website/content/en/preview/concepts/disruption.md:131-175; every
+                                            candidate is one simulation of ONE plan.drift batch)
+  Controller.compute_command(cluster, plan) one disruption pass in upstream order ("first Drift then Consolidation",
+                                            disruption.md:16-27; Emptiness, Drift, MultiNodeConsolidation,
                                             SingleNodeConsolidation): the first method that returns a command wins
 
 NodePool disruption budgets (R:website/content/en/preview/concepts/disruption.md:274-333,
@@ -34,7 +39,7 @@ R:pkg/apis/crds/karpenter.sh_nodepools.yaml:95-135), modelled when a NodePool ca
   admissible(cluster, offsets, nodes, allowed)  the sweep's generalisation: a subset is admissible iff no NodePool owns
                                             more of its members than allowed[pool] (what the device gate computes)
 
-Emptiness asks with the reason Empty, single- and multi-node consolidation with Underutilized. NodePool.budgets None is
+Emptiness asks with the reason Empty, single- and multi-node consolidation with Underutilized, Drift with Drifted. NodePool.budgets None is
 "not modelled": unlimited, and nothing above runs.
 
 Decisions are kp_decision values: 0 no-op, 1 delete, 2 replace.
@@ -271,8 +276,51 @@ class Emptiness:
         return Command("emptiness", empty, DELETE, {"decision": DELETE}) if empty else None
 
 
+def drift_order(cluster):
+    """Drift candidates: the nodes carrying a Drifted condition (ClusterNode.drifted, its transition time) and not
+    marked for deletion, oldest condition first, ties by node name."""
+    idx = [i for i, n in enumerate(cluster.nodes) if getattr(n, "drifted", None) is not None and not n.deleting]
+    return sorted(idx, key=lambda i: (cluster.nodes[i].drifted, cluster.nodes[i].node.name))
+
+
+class Drift:
+    """Drift (upstream disruption/drift.go v1.5.1, restated in DESIGN §10). Budgets are asked with the reason Drifted.
+    Drifted candidates without reschedulable pods come first: each whose pool still has allowance is kept (one
+    allowance each) and, if any are kept, they form one DELETE command with no simulation. Otherwise the candidates are
+    tried in order, one whose pool's allowance is 0 skipped; the first whose simulation schedules every non-pending pod
+    wins, with every new NodeClaim of that Solve as its replacements (none: a plain delete). All candidates are one
+    plan.drift batch of singletons: the device answers which is first."""
+
+    def compute_command(self, cluster, plan, now=None, not_ready=(), extra_deleting=None):
+        cands = drift_order(cluster)
+        if not cands:
+            return None
+        allowed = None
+        if budgets_modelled(cluster):
+            allowed = allowed_disruptions(cluster, DRIFTED, now, not_ready, extra_deleting)
+        empty = [c for c in cands if not cluster.nodes[c].pods]
+        if empty and allowed is not None:
+            empty = budget_walk(cluster, empty, allowed)
+        if empty:
+            return Command("drift", empty, DELETE, {"decision": DELETE, "replacements": [], "blocked": []})
+        if allowed is not None:  # a candidate whose pool's allowance is 0 is skipped (nothing is consumed before a command)
+            pools = node_pools(cluster)
+            cands = [c for c in cands if allowed[int(pools[c])] != 0]
+        if not cands:
+            return None
+        r = plan.drift([[c] for c in cands], allowed=allowed)
+        if r["first"] < 0:
+            return None
+        repl = r["replacements"]["nodeclaims"]
+        decision = REPLACE if repl else DELETE
+        return Command("drift", [cands[r["first"]]], decision,
+                       {"decision": decision, "replacements": repl, "placement": r["replacements"]["placement"],
+                        "blocked": cands[:r["first"]]})
+
+
 class Controller:
-    """One pass of the disruption controller over the consolidation methods, in upstream order: Emptiness, then
+    """One pass of the disruption controller over its methods, in upstream order: Emptiness, then Drift (only when some
+    node carries `drifted`; the plan is not touched otherwise), then
     MultiNodeConsolidation (firstNConsolidationOption over the disruption-cost order), then SingleNodeConsolidation
     (the first candidate whose computeConsolidation is not a no-op). plan: the resident snapshot of `cluster`
     (ClusterPlan, or any object with the same simulate(subsets, multi_node)). When some NodePool has budgets, each
@@ -282,6 +330,9 @@ class Controller:
     def compute_command(self, cluster, plan, now=None, not_ready=(), extra_deleting=None):
         cands = candidate_order(cluster)
         cmd = Emptiness().compute_command(cluster, cands, now, not_ready, extra_deleting)
+        if cmd is not None:
+            return cmd
+        cmd = Drift().compute_command(cluster, plan, now, not_ready, extra_deleting)
         if cmd is not None:
             return cmd
         cands = [c for c in cands if cluster.nodes[c].pods]

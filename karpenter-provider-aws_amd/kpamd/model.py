@@ -138,6 +138,7 @@ class ClusterNode:
     instance_type: int
     pods: List[int] = field(default_factory=list)   # indices into Cluster.pod_*
     deleting: bool = False                           # MarkedForDeletion: its pods join every simulation
+    drifted: Optional[float] = None                  # transition time of its Drifted condition (None: not drifted)
 
 
 @dataclass
