@@ -24,6 +24,8 @@
  *   kp_cluster_simulate / kp_consolidate_argmin <- upstream disruption computeConsolidation over candidate subsets
  *                             (R:website/content/en/preview/concepts/disruption.md:89-128); the _budgeted forms also
  *                             apply the NodePools' disruption budgets (disruption.md:274-333) per subset on the device.
+ *   kp_cluster_command     <- the Command computeConsolidation returns: the replacement NodeClaim (options after the
+ *                             price filters, requirements, requests, pods) and where every rescheduled pod went.
  *
  * Conventions
  *   - Every function returns int32: KP_OK (0) or a negative KP_E_* code. kp_last_error() gives text.
@@ -944,6 +946,34 @@ typedef struct kp_drift_result {
 int32_t kp_cluster_drift(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
                          uint32_t n_subsets, const uint32_t* allowed, uint32_t n_allowed, kp_drift_result* out,
                          int64_t* first, kp_solve_result** replacements, uint64_t* n_blocked, kp_solve_stats* stats);
+/* The consolidation command (upstream computeConsolidation's Command and its scheduling results: the replacement
+ * NodeClaim the disruption controller launches, R:website/content/en/preview/concepts/disruption.md:89-128; upstream
+ * disruption/consolidation.go computeConsolidation, filterByPrice, filterOutSameType and the spot-to-spot branch),
+ * additive to ABI v13. Inputs, the budget rule and the errors are those of kp_cluster_simulate_budgeted, and out[s] is
+ * exactly what that call writes for subset s. commands[s] (n_subsets entries) is the decision's command, owned by the
+ * caller (kp_result_destroy) and read with the kp_result_* accessors:
+ *   NOOP, or blocked by a budget: NULL.
+ *   DELETE: a result with no NodeClaim and the placements.
+ *   REPLACE: exactly one NodeClaim. options: the command's InstanceTypeOptions - of the NodeClaim's truncated,
+ *     price-ordered options (cheapest compatible offering ascending, then name) those that survived filterByPrice and,
+ *     with multi_node, filterOutSameType; for a single spot candidate under the spot-to-spot gate the first 15 of them
+ *     (the first 100 when the requirements carry minValues); n_options equals out[s].n_options. n_remaining: the
+ *     NodeClaim's options before truncation, as in a Solve. requirements: rendered as kp_solve_run renders them; when
+ *     the decision was taken as spot-to-spot (every candidate spot, the replacement admits spot)
+ *     karpenter.sh/capacity-type In [spot] replaces any other capacity-type requirement. requests, nodepool and pods
+ *     (in add order) as in a Solve.
+ *   Placements follow kp_cluster_drift's convention: indexed by the simulation's input order (pending pods, the
+ *     deleting nodes' pods in node order, the subset's pods in subset order); >= 0 the NodeClaim, <= -2 existing node
+ *     -2 - placement among the nodes neither in the subset nor being deleted, in cluster order, -1 unscheduled.
+ * The command comes from the run that takes the decision: on a plan of the batched simulation kernel the emitting
+ * sim_kernel instantiation writes one record per simulation (sized from the batch; a call whose records would pass
+ * 4 GiB returns KP_E_UNSUPPORTED); on a general-path plan it is read from the simulation's arena of the batched launch,
+ * or from the Solve of a subset compiled on its own (stats as kp_cluster_simulate reports them). The call is meant for
+ * the few subsets a pass ends on (the firstN pick, the first single-node hit, the sweep's argmax). On any error every
+ * commands[s] is NULL. */
+int32_t kp_cluster_command(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
+                           uint32_t n_subsets, int32_t multi_node, const uint32_t* allowed, uint32_t n_allowed,
+                           kp_sim_result* out, kp_solve_result** commands, uint64_t* n_blocked, kp_solve_stats* stats);
 /* The reduction kp_consolidate_argmin applies to the gathered per-rank records (host-only; exposed for callers that
  * reduce over another transport, and for tests): counts are summed, the best record wins. */
 int32_t kp_choice_reduce(const kp_choice* per_rank, uint32_t n, kp_choice* out);

@@ -422,12 +422,40 @@ struct SimArgs {
 // admissible ones, ascending
 struct SimAll {
   static constexpr bool gated = false;
+  static constexpr bool emit = false;
   static constexpr const uint32_t* live = nullptr;
 };
 struct SimLive {
   static constexpr bool gated = true;
+  static constexpr bool emit = false;
   const uint32_t* live;
 };
+// The emitting instantiation (kp_cluster_command): gated as SimLive, and every simulation also leaves the command it
+// decided on in its subset's record, rec + stride * subset: a SimCmdHdr, then three [cap] arrays over the simulation's
+// queue positions (the order its pods were sorted into): the pod's global queue rank (uint32), its placement at commit
+// (int32: 0 the NodeClaim, <= -2 existing position -2 - p, -1 never placed), and the NodeClaim's add order (uint32 queue
+// positions, n_added of them). Each word has one writer and is a plain vector store.
+#define SIM_CMD_OPTS 128  // >= SimArgs.max_types (100): the two 64-lane halves of the truncated option list
+struct SimCmdHdr {
+  int32_t tmpl;          // REPLACE: the NodeClaim's template
+  uint32_t n_remaining;  // its instance-type options before truncation
+  uint32_t n_kept;       // options[] entries: what the price filters (and the spot-to-spot cut) kept, price order
+  uint32_t s2s;          // the decision was taken as spot-to-spot
+  uint32_t n_queue;      // pods the simulation queued (every decision)
+  uint32_t n_added;      // pods the NodeClaim took (every decision)
+  uint32_t pad_[2];
+  uint32_t options[SIM_CMD_OPTS];
+  int64_t requests[KP_NRES];
+  KReqs reqs;
+};
+struct SimEmit {
+  static constexpr bool gated = true;
+  static constexpr bool emit = true;
+  const uint32_t* live;
+  uint8_t* rec;
+  size_t stride;  // sim_cmd_stride(cap)
+};
+inline size_t sim_cmd_stride(int cap) { return (sizeof(SimCmdHdr) + (size_t)12 * cap + 15) & ~(size_t)15; }
 // budget gate over the resident CSR batch (budget_gate_kernel, gate_scan_kernel, gate_scatter_kernel)
 #define GATE_WAVES 4
 #define GATE_PER_WAVE 16
@@ -510,6 +538,9 @@ hipError_t launch_sim(const SimArgs& a, int blocks, size_t dyn_lds, hipStream_t 
 // the gated instantiation (disruption budgets): the waves walk live[0 .. n_live), the admissible subsets, ascending
 hipError_t launch_sim_gated(const SimArgs& a, const uint32_t* live, int n_live, int blocks, size_t dyn_lds, hipStream_t s);
 const void* sim_kernel_ptr(bool gated = false);
+// the emitting instantiation (kp_cluster_command): as launch_sim_gated, with the command records
+hipError_t launch_sim_emit(const SimArgs& a, const SimEmit& em, int n_live, int blocks, size_t dyn_lds, hipStream_t s);
+const void* sim_emit_kernel_ptr();
 #define SIM_WAVES 4
 
 hipError_t launch_solve(const SolveArgs& a, int nw, size_t dyn_lds, hipStream_t s);

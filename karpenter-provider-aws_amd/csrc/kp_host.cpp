@@ -4799,6 +4799,7 @@ struct kp_cluster_plan {
   bool gb_tried = false;
   uint32_t general_batched = 0;           // simulations of the last general batch that ran batched
   uint64_t sim_waves[2] = {0, 0};         // the last batched sweep: wave slots launched, most subsets any wave ran
+  vector<uint32_t> cmd_live;              // kp_cluster_command without budgets: the identity list its launch walks
   std::unique_ptr<Compiled> cp;
   DevBuf buf;                       // resident snapshot
   DevBuf scratch;                   // per-wave state, grown on demand
@@ -5469,7 +5470,8 @@ struct CandCache {
 static void GeneralDecide(const kp_cluster& cl, const vector<std::map<string, string>>& labels,
                           const vector<uint32_t>& cand, const SolveBase& B, bool all, int n_nc, const KReqs* R,
                           int ci, uint32_t nodepool, const uint32_t* opts, uint32_t n_opts, int32_t multi_node,
-                          SimOut& r, const OfferTab* tab = nullptr, const CandCache* cc = nullptr) {
+                          SimOut& r, const OfferTab* tab = nullptr, const CandCache* cc = nullptr,
+                          vector<int>* kept_out = nullptr, bool* s2s_out = nullptr) {
   double candPrice = 0;
   bool priced = true, allSpot = true;
   for (uint32_t c : cand) {
@@ -5552,6 +5554,8 @@ static void GeneralDecide(const kp_cluster& cl, const vector<std::map<string, st
   r.replacement_price = best;
   r.savings = candPrice - best;
   r.n_options = (uint32_t)kept.size();
+  if (kept_out) kept_out->assign(kept.begin(), kept.end());  // the command's InstanceTypeOptions, price order
+  if (s2s_out) *s2s_out = s2s;
 }
 
 // One subset's SimulateScheduling as its own Solve: compiled on the host from the subset's inputs (the path for
@@ -5636,8 +5640,12 @@ static int32_t GeneralSolveOne(kp_cluster_plan* plan, const vector<uint32_t>& ca
   *dev_ms += res->stats.device_ms;
   return KP_OK;
 }
+static void NarrowToSpot(const Dict& d, KReqs& q);
+// command (kp_cluster_command): where to leave the decision's command, the Solve's own result cut to the options the
+// decision kept; its placements are already in the simulation's input order and name the Solve's existing nodes
 static int32_t GeneralSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand, const vector<std::map<string, string>>& labels,
-                             int32_t multi_node, SimOut& r, uint64_t* counters, double* dev_ms, kp_cancel* cancel) {
+                             int32_t multi_node, SimOut& r, uint64_t* counters, double* dev_ms, kp_cancel* cancel,
+                             kp_solve_result** command = nullptr) {
   SimOneSolve so;
   if (int32_t rc = GeneralSolveOne(plan, cand, so, counters, dev_ms, cancel)) return rc;
   const kp_cluster& cl = plan->cluster()->cl;
@@ -5654,10 +5662,23 @@ static int32_t GeneralSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand
     else if (kind[p] == 0 && pl <= -2 && !ex[(size_t)(-2 - pl)].initialized) all = false;
   }
   const int n_nc = (int)res->ncs.size();
+  vector<int> kept;
+  bool s2s = false;
   // (kp_solve_run already applied the held reservations and the minValues truncation check to NodeClaim 0)
   GeneralDecide(cl, labels, cand, *so.sp->cp->B, all, n_nc, n_nc ? &res->fin[0] : nullptr, n_nc ? res->nc_cat[0] : 0,
                 n_nc ? res->ncs[0].nodepool : 0, n_nc ? res->ncs[0].options.data() : nullptr,
-                n_nc ? (uint32_t)res->ncs[0].options.size() : 0, multi_node, r);
+                n_nc ? (uint32_t)res->ncs[0].options.size() : 0, multi_node, r, nullptr, nullptr, &kept, &s2s);
+  if (command && r.decision != KP_DECISION_NOOP) {
+    kp_solve_result* cr = so.res.release();
+    if (r.decision == KP_DECISION_REPLACE) {
+      cr->ncs[0].options.assign(kept.begin(), kept.end());
+      if (s2s) {
+        NarrowToSpot(so.sp->cp->B->d, cr->fin[0]);
+        cr->ncs[0].reqs = DecodeReqs(so.sp->cp->B->d, cr->fin[0]);
+      }
+    }
+    *command = cr;
+  }
   return KP_OK;
 }
 
@@ -6079,7 +6100,8 @@ static int32_t DriftFetch(kp_cluster_plan* plan, GeneralBatch& gb, const GenSlot
 static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const vector<vector<uint32_t>>& cands,
                                const vector<int>& idx, const vector<std::map<string, string>>& labels, int32_t multi_node,
                                vector<SimOut>& outs, uint64_t* counters, double* dev_ms, double* host_ms,
-                               kp_cancel* cancel, uint64_t* n_launches, DriftRun* dr = nullptr) {
+                               kp_cancel* cancel, uint64_t* n_launches, DriftRun* dr = nullptr,
+                               kp_solve_result** commands = nullptr) {
   kp_ctx* ctx = plan->ctx;
   const kp_cluster& cl = plan->cluster()->cl;
   const Compiled& C = *gb.C;
@@ -6173,6 +6195,9 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
     const vector<vector<int32_t>>& queues = sl.queues;
     std::atomic<int> bad_runaway{-1}, cancelled{0};
     uint64_t tcount[kMaxHostThreads][3] = {}, tphase[kMaxHostThreads][8] = {};
+    // kp_cluster_command: the options each decision kept and whether it was taken as spot-to-spot
+    vector<vector<int>> keptv(commands ? n : 0);
+    vector<uint8_t> s2sv(commands ? n : 0, 0);
     ParallelFor(n, [&](int j_lo, int j_hi, int t) {
     for (int j = j_lo; j < j_hi; j++) {
       const int i = order[b0 + j];
@@ -6210,8 +6235,10 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
         ci = C.B->tmpl_catalog[nct[j]];
         np = (uint32_t)C.B->tmpl_nodepool[nct[j]];
       }
+      bool s2s = false;
       GeneralDecide(cl, labels, cands[i], *C.B, all, n_nc, &R, ci, np, &opts[(size_t)j * gb.opt_stride],
-                    n_nc == 1 ? nopt[j] : 0, multi_node, r, &gb.offers, &gb.cands);
+                    n_nc == 1 ? nopt[j] : 0, multi_node, r, &gb.offers, &gb.cands, commands ? &keptv[j] : nullptr, &s2s);
+      if (commands) s2sv[j] = s2s ? 1 : 0;
     }
     });
     for (int t = 0; t < kMaxHostThreads; t++) {
@@ -6221,6 +6248,27 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
     if (bad_runaway >= 0)
       return fail(KP_E_DEVICE, "solve_kernel exceeded its Queue.Pop bound in simulation %d: aborted", bad_runaway.load());
     if (cancelled) return fail(KP_E_CANCELED, "consolidation simulations cancelled (kp_cancel_set)");
+    // kp_cluster_command: the command of every simulation that decided DELETE or REPLACE, from its arena while the
+    // slot still holds it (the launch after the next overwrites it, and is not queued yet), as drift mode reads its
+    // winner: FetchArenaResult + AssembleResult, then the NodeClaim's options cut to the ones the decision kept. A
+    // simulation that stopped at its second NodeClaim decided no-op and is not read.
+    for (int j = 0; commands && j < n; j++) {
+      const int i = order[b0 + j];
+      if (outs[i].decision == KP_DECISION_NOOP) continue;
+      std::unique_ptr<kp_solve_result> res;
+      if (int32_t rc = DriftFetch(plan, gb, sl, j, cands[i], res)) return rc;
+      const bool replace = outs[i].decision == KP_DECISION_REPLACE;
+      if (res->ncs.size() != (replace ? 1u : 0u))
+        return fail(KP_E_DEVICE, "command of subset %d: %zu NodeClaims in its arena", i, res->ncs.size());
+      if (replace) {
+        res->ncs[0].options.assign(keptv[j].begin(), keptv[j].end());
+        if (s2sv[j]) {
+          NarrowToSpot(C.B->d, res->fin[0]);
+          res->ncs[0].reqs = DecodeReqs(C.B->d, res->fin[0]);
+        }
+      }
+      commands[i] = res.release();
+    }
     host_ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th1).count();
     return KP_OK;
   };
@@ -6307,7 +6355,8 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
       }
       for (size_t j = b0; j < idx.size(); j++)
         if (int32_t rc = dr ? DriftSimOne(plan, cands[order[j]], order[j], *dr, counters, dev_ms, cancel)
-                            : GeneralSimOne(plan, cands[order[j]], labels, multi_node, outs[order[j]], counters, dev_ms, cancel))
+                            : GeneralSimOne(plan, cands[order[j]], labels, multi_node, outs[order[j]], counters, dev_ms, cancel,
+                                            commands ? &commands[order[j]] : nullptr))
           return rc;
       break;
     }
@@ -6598,7 +6647,8 @@ static int32_t GeneralPartition(kp_cluster_plan* plan, const uint32_t* offsets, 
 }
 
 static int32_t GeneralSimLocked(kp_cluster_plan* plan, const uint32_t* offsets, const uint32_t* nodes,
-                                uint32_t n_subsets, int32_t multi_node, SimArgs& a, kp_cancel* cancel, BudgetGate* bg) {
+                                uint32_t n_subsets, int32_t multi_node, SimArgs& a, kp_cancel* cancel, BudgetGate* bg,
+                                kp_solve_result** commands = nullptr) {
   kp_ctx* ctx = plan->ctx;
   const kp_cluster& cl = plan->general->cl;
   const int N = (int)cl.n_nodes;
@@ -6625,13 +6675,14 @@ static int32_t GeneralSimLocked(kp_cluster_plan* plan, const uint32_t* offsets, 
   const auto t1 = clk::now();
   if (!batched.empty()) {
     const int32_t rc = GeneralBatchRun(plan, *plan->gb, cands, batched, labels, multi_node, outs, counters, &dev_ms, host_ms,
-                                       cancel, &n_launches);
+                                       cancel, &n_launches, nullptr, commands);
     if (rc) return rc;
   }
   const double t_batch = std::chrono::duration<double, std::milli>(clk::now() - t1).count();
   const auto t2 = clk::now();
   for (int s : single) {
-    const int32_t rc = GeneralSimOne(plan, cands[s], labels, multi_node, outs[s], counters, &dev_ms, cancel);
+    const int32_t rc = GeneralSimOne(plan, cands[s], labels, multi_node, outs[s], counters, &dev_ms, cancel,
+                                     commands ? &commands[s] : nullptr);
     if (rc) return rc;
   }
   const double t_single = std::chrono::duration<double, std::milli>(clk::now() - t2).count();
@@ -6863,8 +6914,16 @@ int32_t kp_cluster_drift(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_
   return rc;
 }
 
+// kp_cluster_command on a plan of the batched kernel: where the launch left the subsets' command records
+struct CmdEmit {
+  const uint8_t* rec = nullptr;  // [n_subsets] records (device), sim_cmd_stride(cap) bytes each
+  size_t stride = 0;
+  int cap = 0;
+  kp_solve_result** commands = nullptr;  // general-path plans: filled from the batched launches' arenas
+};
 static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, const uint32_t* nodes, uint32_t n_subsets,
-                               int32_t multi_node, SimArgs& a_out, kp_cancel* cancel, BudgetGate* bg = nullptr) {
+                               int32_t multi_node, SimArgs& a_out, kp_cancel* cancel, BudgetGate* bg = nullptr,
+                               CmdEmit* em = nullptr) {
   kp_ctx* ctx = plan->ctx;
   if (cancel && __atomic_load_n(cancel->flag, __ATOMIC_SEQ_CST))
     return fail(KP_E_CANCELED, "cancelled before the simulations");
@@ -6872,7 +6931,8 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
     if (int32_t rc = CheckBudget(plan, bg)) return rc;
     bg->blocked = 0;
   }
-  if (plan->general) return GeneralSimLocked(plan, offsets, nodes, n_subsets, multi_node, a_out, cancel, bg);
+  if (plan->general)
+    return GeneralSimLocked(plan, offsets, nodes, n_subsets, multi_node, a_out, cancel, bg, em ? em->commands : nullptr);
   if (int32_t rc = CatalogsAlive(plan->cp->B->alive)) return rc;
   if (SeqnumsOf(plan->cp->B->catalogs) != plan->cp->B->seqnums)
     return fail(KP_E_INVAL, "stale plan: a catalogue's seqnum changed since it was prepared (kp_cluster_refresh)");
@@ -6909,7 +6969,7 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
     a.cancel = (const int32_t*)dp;
   }
   hipFuncAttributes fa;
-  HIPCHK(hipFuncGetAttributes(&fa, sim_kernel_ptr(bg != nullptr)));
+  HIPCHK(hipFuncGetAttributes(&fa, em ? sim_emit_kernel_ptr() : sim_kernel_ptr(bg != nullptr)));
   const size_t lds_wg = fa.sharedSizeBytes + (size_t)SIM_WAVES * a.wave_lds;
   if (lds_wg > 160 * 1024) return fail(KP_E_UNSUPPORTED, "simulation LDS %zu B per workgroup (cluster or subsets too large)", lds_wg);
   const int wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds_wg));
@@ -6957,9 +7017,17 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
   const size_t b_out = al(sizeof(SimOut) * n_subsets);
   // the budget gate's regions: gate bytes, live list, block counts and offsets, allowed[], the live count
   const uint32_t n_gblk = (n_subsets + GATE_BLOCK - 1) / GATE_BLOCK;
-  const size_t g_gate = bg ? al(n_subsets) : 0, g_live = bg ? al(sizeof(uint32_t) * n_subsets) : 0;
+  const size_t g_gate = bg ? al(n_subsets) : 0, g_live = bg || em ? al(sizeof(uint32_t) * n_subsets) : 0;
   const size_t g_blk = bg ? al(sizeof(uint32_t) * n_gblk) : 0, g_allowed = bg ? al(sizeof(uint32_t) * (plan->n_pools + 1)) : 0;
-  const size_t b_total = b_off + b_nodes + b_out + g_gate + g_live + 2 * g_blk + g_allowed + (bg ? 256 : 0);
+  // the command records (kp_cluster_command), sized from the batch: behind everything else
+  const size_t o_rec = b_off + b_nodes + b_out + g_gate + g_live + 2 * g_blk + g_allowed + (bg ? 256 : 0);
+  const size_t rec_stride = em ? sim_cmd_stride(cap) : 0;
+  // (the call is meant for the few subsets a pass ends on; a batch whose records would not fit a 32-bit byte count is
+  // handed back rather than run in parts)
+  if (em && rec_stride * (size_t)n_subsets > ((size_t)4 << 30))
+    return fail(KP_E_UNSUPPORTED, "%u subsets of up to %d pods: %zu B of command records (max 4 GiB per call)", n_subsets, cap,
+                rec_stride * (size_t)n_subsets);
+  const size_t b_total = o_rec + al(rec_stride * n_subsets);
   if (b_total > plan->batch_bytes) {
     if (plan->batch.p) HIPCHK(hipFree(plan->batch.p));
     plan->batch.p = nullptr;
@@ -6976,6 +7044,12 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
   if (n_flat) HIPCHK(hipMemcpyAsync(bb + b_off, nodes, sizeof(uint32_t) * n_flat, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(a.s_ncfail, 0xFF, sz_fail, st));
   HIPCHK(hipMemsetAsync(a.stats, 0, sizeof(uint64_t) * 8, st));
+  SimEmit se{nullptr, bb + o_rec, rec_stride};
+  if (em) {
+    em->rec = bb + o_rec;
+    em->stride = rec_stride;
+    em->cap = cap;
+  }
   if (bg) {
     // the gate on the resident batch, then the live count (4 bytes) sizes the simulation grid
     uint8_t* gp = bb + b_off + b_nodes + b_out;
@@ -7007,7 +7081,23 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
     plan->sim_waves[0] = n_live ? (uint64_t)a.n_slots : 0;  // (no live subset: nothing is launched)
     plan->sim_waves[1] = (n_live + (uint32_t)a.n_slots - 1) / (uint32_t)a.n_slots;
     HIPCHK(hipEventRecord(ctx->ev0, st));
-    if (n_live) HIPCHK(launch_sim_gated(a, g.live, (int)n_live, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
+    se.live = g.live;
+    if (n_live && em) HIPCHK(launch_sim_emit(a, se, (int)n_live, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
+    else if (n_live) HIPCHK(launch_sim_gated(a, g.live, (int)n_live, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
+    HIPCHK(hipEventRecord(ctx->ev1, st));
+    return KP_OK;
+  }
+  if (em) {
+    // No budgets: the emitting instantiation walks every subset, in order, through an identity list. An ungated
+    // emitting policy would be a fourth sim_kernel instantiation (its own code object and resource figures to hold)
+    // to save one 4 * n_subsets byte upload on a call made for a few subsets.
+    uint32_t* live = (uint32_t*)(bb + b_off + b_nodes + b_out);
+    plan->cmd_live.resize(n_subsets);
+    for (uint32_t s = 0; s < n_subsets; s++) plan->cmd_live[s] = s;
+    HIPCHK(hipMemcpyAsync(live, plan->cmd_live.data(), sizeof(uint32_t) * n_subsets, hipMemcpyHostToDevice, st));
+    se.live = live;
+    HIPCHK(hipEventRecord(ctx->ev0, st));
+    HIPCHK(launch_sim_emit(a, se, (int)n_subsets, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
     HIPCHK(hipEventRecord(ctx->ev1, st));
     return KP_OK;
   }
@@ -7024,7 +7114,136 @@ int32_t kp_cluster_simulate(kp_cluster_plan* plan, const uint32_t* offsets, cons
 
 static int32_t SimulateImpl(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
                             uint32_t n_subsets, int32_t multi_node, kp_sim_result* out, kp_solve_stats* stats,
-                            BudgetGate* bg);
+                            BudgetGate* bg, kp_solve_result** commands = nullptr);
+
+// The spot-to-spot branch of computeConsolidation: the replacement launches spot only, so
+// karpenter.sh/capacity-type In [spot] replaces whatever the NodeClaim required of the capacity type.
+static void NarrowToSpot(const Dict& d, KReqs& q) {
+  const int k = d.key(kCapType);
+  const int bit = k >= 0 ? d.bit(k, "spot") : -1;
+  if (bit < 0) return;
+  for (int wi = 0; wi < nwords(d, k); wi++) q.vals[kw(d, k, wi)] = 0;
+  q.vals[bit / 64] |= 1ull << (bit % 64);
+  q.present |= 1ull << k;
+  q.compl_ &= ~(1ull << k);
+  q.hgt &= ~(1ull << k), q.hlt &= ~(1ull << k), q.hmin &= ~(1ull << k);
+}
+
+// The simulation's input order and existing-node index, as kp_abi.h states them for kp_cluster_drift's replacements and
+// kp_cluster_command's commands: pending pods, the deleting nodes' pods in node order, the subset's pods in subset
+// order; the nodes neither in the subset nor being deleted, in cluster order.
+struct CommandIndex {
+  const kp_cluster& cl;
+  vector<int32_t> pod_idx;     // [P] input index of a queued pod, -1
+  vector<int32_t> del_before;  // [N + 1] deleting nodes before node i
+  vector<uint32_t> sorted;     // the current subset's nodes, ascending
+  vector<uint32_t> cand_pods;
+  int n_base = 0;
+  explicit CommandIndex(const kp_cluster& c) : cl(c), pod_idx(std::max<uint32_t>(c.n_pods, 1), -1), del_before(c.n_nodes + 1, 0) {
+    for (uint32_t j = 0; j < cl.n_pending; j++) pod_idx[cl.pending_pods[j]] = n_base++;
+    for (uint32_t i = 0; i < cl.n_nodes; i++) {
+      del_before[i + 1] = del_before[i] + (cl.nodes[i].deleting ? 1 : 0);
+      if (cl.nodes[i].deleting)
+        for (uint32_t j = 0; j < cl.nodes[i].n_pods; j++) pod_idx[cl.nodes[i].pods[j]] = n_base++;
+    }
+  }
+  int Enter(const uint32_t* cand, uint32_t n) {  // -> pods queued
+    sorted.assign(cand, cand + n);
+    std::sort(sorted.begin(), sorted.end());
+    int k = n_base;
+    for (uint32_t i = 0; i < n; i++)
+      for (uint32_t j = 0; j < cl.nodes[cand[i]].n_pods; j++) {
+        cand_pods.push_back(cl.nodes[cand[i]].pods[j]);
+        pod_idx[cand_pods.back()] = k++;
+      }
+    return k;
+  }
+  void Leave() {
+    for (uint32_t p : cand_pods) pod_idx[p] = -1;
+    cand_pods.clear();
+  }
+  int Existing(uint32_t node) const {  // -1: in the subset or being deleted
+    if (node >= cl.n_nodes || cl.nodes[node].deleting) return -1;
+    auto it = std::lower_bound(sorted.begin(), sorted.end(), node);
+    if (it != sorted.end() && *it == node) return -1;
+    return (int)node - del_before[node] - (int)(it - sorted.begin());
+  }
+};
+
+// kp_cluster_command on a plan of the batched kernel: the commands of the subsets that decided DELETE or REPLACE, from
+// the records the emitting sim_kernel left (recs: their host copy). Existing positions become the ABI's existing
+// index, queue positions the simulation's input order, the spot-to-spot narrowing is applied and the requirements
+// are rendered as AssembleResult renders a Solve's.
+static int32_t BuildSimCommands(kp_cluster_plan* plan, const uint32_t* offsets, const uint32_t* nodes, uint32_t n_subsets,
+                                const kp_sim_result* out, const uint8_t* recs, const CmdEmit& em, kp_solve_result** commands) {
+  const Compiled& C = *plan->cp;
+  const SolveBase& B = *C.B;
+  const Dict& d = B.d;
+  if (!plan->owned) return fail(KP_E_INVAL, "the plan keeps no cluster");
+  CommandIndex ix(plan->owned->cl);
+  const uint32_t P = plan->owned->cl.n_pods;
+  for (uint32_t s = 0; s < n_subsets; s++) {
+    if (out[s].decision == KP_DECISION_NOOP) continue;
+    const SimCmdHdr* h = reinterpret_cast<const SimCmdHdr*>(recs + em.stride * s);
+    const uint32_t* rq = reinterpret_cast<const uint32_t*>(h + 1);
+    const int32_t* rp = reinterpret_cast<const int32_t*>(rq + em.cap);
+    const uint32_t* ro = reinterpret_cast<const uint32_t*>(rp + em.cap);
+    const bool replace = out[s].decision == KP_DECISION_REPLACE;
+    const int nq = ix.Enter(nodes + offsets[s], offsets[s + 1] - offsets[s]);
+    struct Exit {
+      CommandIndex& ix;
+      ~Exit() { ix.Leave(); }
+    } exit_{ix};
+    if ((int)h->n_queue != nq || nq > em.cap || (int)h->n_added > nq)
+      return fail(KP_E_DEVICE, "command record of subset %u: %u pods queued (%d expected), %u added", s, h->n_queue, nq, h->n_added);
+    auto res = std::make_unique<kp_solve_result>();
+    memset(&res->stats, 0, sizeof res->stats);
+    res->placement.assign(nq, -1);
+    vector<int32_t> at(nq, -1);  // queue position -> input index
+    for (int i = 0; i < nq; i++) {
+      const int32_t idx = rq[i] < P ? ix.pod_idx[C.queue[rq[i]]] : -1;
+      if (idx < 0 || idx >= nq) return fail(KP_E_DEVICE, "command record of subset %u: queue position %d names rank %u", s, i, rq[i]);
+      at[i] = idx;
+      const int32_t pl = rp[i];
+      if (pl == 0 && replace) {
+        res->placement[idx] = 0;
+      } else if (pl <= -2) {
+        const int pos = -2 - pl;
+        const int e = pos < (int)C.ex_input.size() ? ix.Existing((uint32_t)C.ex_input[pos]) : -1;
+        if (e < 0) return fail(KP_E_DEVICE, "command record of subset %u: a pod on existing position %d", s, pos);
+        res->placement[idx] = -2 - e;
+      } else if (pl != -1) {
+        return fail(KP_E_DEVICE, "command record of subset %u: placement %d", s, pl);
+      }
+    }
+    if (replace) {
+      if (h->tmpl < 0 || h->tmpl >= (int)B.tmpl_catalog.size() || h->n_kept > SIM_CMD_OPTS || h->n_kept != out[s].n_options)
+        return fail(KP_E_DEVICE, "command record of subset %u: template %d, %u options (%u decided)", s, h->tmpl, h->n_kept,
+                    out[s].n_options);
+      res->ncs.resize(1);
+      auto& nc = res->ncs[0];
+      nc.nodepool = (uint32_t)B.tmpl_nodepool[h->tmpl];
+      nc.n_remaining = h->n_remaining;
+      nc.options.assign(h->options, h->options + h->n_kept);
+      memset(&nc.requests, 0, sizeof nc.requests);
+      for (int r = 0; r < KP_NRES; r++) {
+        nc.requests.milli[r] = h->requests[r];
+        if (nc.requests.milli[r]) nc.requests.present |= 1u << r;
+      }
+      for (uint32_t j = 0; j < h->n_added; j++) {
+        if (ro[j] >= (uint32_t)nq) return fail(KP_E_DEVICE, "command record of subset %u: add %u names position %u", s, j, ro[j]);
+        nc.pods.push_back((uint32_t)at[ro[j]]);
+      }
+      KReqs fin = h->reqs;
+      if (h->s2s) NarrowToSpot(d, fin);
+      nc.reqs = DecodeReqs(d, fin);
+      res->fin.push_back(fin);
+      res->nc_cat.push_back(B.tmpl_catalog[h->tmpl]);
+    }
+    commands[s] = res.release();
+  }
+  return KP_OK;
+}
 
 int32_t kp_cluster_simulate_cancellable(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets,
                                         const uint32_t* nodes, uint32_t n_subsets, int32_t multi_node, kp_sim_result* out,
@@ -7046,7 +7265,7 @@ int32_t kp_cluster_simulate_budgeted(kp_cluster_plan* plan, kp_cancel* cancel, c
 
 static int32_t SimulateImpl(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
                             uint32_t n_subsets, int32_t multi_node, kp_sim_result* out, kp_solve_stats* stats,
-                            BudgetGate* bg) {
+                            BudgetGate* bg, kp_solve_result** commands) {
   auto t0 = std::chrono::steady_clock::now();
   if (!plan || (n_subsets && (!offsets || !out))) return fail(KP_E_INVAL, "null argument");
   if (cancel && cancel->ctx.p != plan->ctx.p) return fail(KP_E_INVAL, "the cancel token belongs to another context");
@@ -7058,10 +7277,17 @@ static int32_t SimulateImpl(kp_cluster_plan* plan, kp_cancel* cancel, const uint
     if (int32_t rc = CheckBudget(plan, bg)) return rc;
   if (n_subsets == 0) return KP_OK;
   SimArgs a;
-  int32_t rc = SimLaunchLocked(plan, offsets, nodes, n_subsets, multi_node, a, cancel, bg);
+  CmdEmit em;
+  em.commands = commands;
+  int32_t rc = SimLaunchLocked(plan, offsets, nodes, n_subsets, multi_node, a, cancel, bg, commands ? &em : nullptr);
   if (rc) return rc;
   hipStream_t st = ctx->stream;
   uint64_t kst[8];
+  vector<uint8_t> recs;  // the command records of a batched-kernel plan
+  if (em.rec) {
+    recs.resize(em.stride * n_subsets);
+    HIPCHK(hipMemcpyAsync(recs.data(), em.rec, recs.size(), hipMemcpyDeviceToHost, st));
+  }
   HIPCHK(hipMemcpyAsync(out, a.out, sizeof(SimOut) * n_subsets, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(kst, a.stats, sizeof kst, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -7070,6 +7296,8 @@ static int32_t SimulateImpl(kp_cluster_plan* plan, kp_cancel* cancel, const uint
   if (!plan->general) HIPCHK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
   for (uint32_t s = 0; s < n_subsets; s++)
     if (out[s].n_pods == 0xFFFFFFFFu) return fail(KP_E_DEVICE, "subset %u overflowed the pod queue", s);
+  if (em.rec)
+    if (int32_t rc2 = BuildSimCommands(plan, offsets, nodes, n_subsets, out, recs.data(), em, commands)) return rc2;
   if (stats) {
     stats->device_ms = ms;
     stats->solve_kernel_ms = ms;
@@ -7088,6 +7316,26 @@ static int32_t SimulateImpl(kp_cluster_plan* plan, kp_cancel* cancel, const uint
     stats->prepare_ms = plan->prepare_ms;
     stats->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
+  return KP_OK;
+}
+
+int32_t kp_cluster_command(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
+                           uint32_t n_subsets, int32_t multi_node, const uint32_t* allowed, uint32_t n_allowed,
+                           kp_sim_result* out, kp_solve_result** commands, uint64_t* n_blocked, kp_solve_stats* stats) {
+  if (n_blocked) *n_blocked = 0;
+  if (n_subsets && !commands) return fail(KP_E_INVAL, "null argument");
+  for (uint32_t s = 0; s < n_subsets; s++) commands[s] = nullptr;
+  BudgetGate bg{allowed, n_allowed};
+  const int32_t rc = SimulateImpl(plan, cancel, offsets, nodes, n_subsets, multi_node, out, stats, allowed ? &bg : nullptr,
+                                  n_subsets ? commands : nullptr);
+  if (rc) {  // no command outlives a failed call
+    for (uint32_t s = 0; s < n_subsets; s++) {
+      kp_result_destroy(commands[s]);
+      commands[s] = nullptr;
+    }
+    return rc;
+  }
+  if (n_blocked && allowed) *n_blocked = bg.blocked;
   return KP_OK;
 }
 

@@ -384,6 +384,22 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
       spod[i] = 0;
     }
     for (int q = lane; q < SL; q += 64) sstart[q] = 0;
+    // the command record (GL::emit): the queue's ranks now (the option sort reuses keys[]), no pod placed yet
+    SimCmdHdr* rh = nullptr;
+    uint32_t* rq = nullptr;
+    int32_t* rp = nullptr;
+    uint32_t* ro = nullptr;
+    int n_add = 0;
+    if constexpr (GL::emit) {
+      rh = reinterpret_cast<SimCmdHdr*>(gl.rec + gl.stride * (size_t)gl.live[sim]);
+      rq = reinterpret_cast<uint32_t*>(rh + 1);
+      rp = reinterpret_cast<int32_t*>(rq + cap);
+      ro = reinterpret_cast<uint32_t*>(rp + cap);
+      for (int i = lane; i < n; i += 64) {
+        rq[i] = keys[i];
+        rp[i] = -1;
+      }
+    }
     sim_sync();
 
     // ---- the Solve loop -------------------------------------------------------------------------
@@ -531,6 +547,13 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
       if (abort) break;
       if (placed != -1) {
         if (kind != 2) placed_cnt++;
+        if constexpr (GL::emit) {  // where the pod went, and the NodeClaim's add order
+          if (lane == 0) {
+            rp[i] = placed;
+            if (placed == 0) ro[n_add] = (uint32_t)i;
+          }
+          if (placed == 0) n_add++;
+        }
       } else {  // Preferences.Relax + Queue.Push
         const bool relaxed = lvl + 1 < a.shape_nlevels[shape];
         int tail = head + len;
@@ -703,6 +726,23 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
             nodepool = a.tmpl_nodepool[nc->tmpl];
             repl = best;
             savings = candPrice - best;
+            if constexpr (GL::emit) {
+              // the kept options in price order: keep[0..1] compacted over the sorted list, the second 64-lane half
+              // behind the first one's count
+              const uint64_t lt = (1ull << lane) - 1;
+              const uint64_t b0 = __ballot(keep[0]), b1 = __ballot(keep[1]);
+              if (keep[0]) rh->options[__popcll(b0 & lt)] = (uint32_t)tt[0];
+              if (keep[1]) rh->options[__popcll(b0) + __popcll(b1 & lt)] = (uint32_t)tt[1];
+              copy_u64(reinterpret_cast<uint64_t*>(&rh->reqs), reinterpret_cast<const uint64_t*>(&nc->reqs),
+                       (int)(sizeof(KReqs) / 8));
+              if (lane < KP_NRES) rh->requests[lane] = nc->requests[lane];
+              if (lane == 0) {
+                rh->tmpl = nc->tmpl;
+                rh->n_remaining = (uint32_t)cnt;
+                rh->n_kept = (uint32_t)n_options;
+                rh->s2s = s2s ? 1u : 0u;
+              }
+            }
           } else {
             n_options = 0;
           }
@@ -719,6 +759,10 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
       o.n_options = (uint32_t)(decision == KP_DECISION_REPLACE ? n_options : 0);
       o.n_pods = overflow ? 0xFFFFFFFFu : (uint32_t)n;
       a.out[GL::gated ? (int)gl.live[sim] : sim] = o;
+      if constexpr (GL::emit) {
+        rh->n_queue = (uint32_t)n;
+        rh->n_added = (uint32_t)n_add;
+      }
     }
     sim_sync();
   }
@@ -752,6 +796,13 @@ hipError_t launch_sim_gated(const SimArgs& a, const uint32_t* live, int n_live, 
   hipLaunchKernelGGL((sim_kernel<SIM_WAVES, SimLive>), dim3(blocks), dim3(SIM_WAVES * 64), dyn_lds, s, al, SimLive{live});
   return hipGetLastError();
 }
+hipError_t launch_sim_emit(const SimArgs& a, const SimEmit& em, int n_live, int blocks, size_t dyn_lds, hipStream_t s) {
+  SimArgs al = a;
+  al.n_subsets = n_live;
+  hipLaunchKernelGGL((sim_kernel<SIM_WAVES, SimEmit>), dim3(blocks), dim3(SIM_WAVES * 64), dyn_lds, s, al, em);
+  return hipGetLastError();
+}
+const void* sim_emit_kernel_ptr() { return reinterpret_cast<const void*>(sim_kernel<SIM_WAVES, SimEmit>); }
 const void* sim_kernel_ptr(bool gated) {
   return gated ? reinterpret_cast<const void*>(sim_kernel<SIM_WAVES, SimLive>)
                : reinterpret_cast<const void*>(sim_kernel<SIM_WAVES, SimAll>);

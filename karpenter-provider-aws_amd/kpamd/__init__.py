@@ -6,6 +6,7 @@ The surfaces mirror the reference's plugin/operator interface for the path:
   compatible_available_filter(...)            <- R:pkg/providers/instance/filter/filter.go:39-64
   ClusterPlan(...).simulate(subsets)          <- upstream disruption computeConsolidation / SimulateScheduling
   ClusterPlan(...).drift(subsets)             <- upstream disruption Drift: SimulateScheduling, the whole Solve
+  ClusterPlan(...).command(subsets)           <- computeConsolidation's Command: the replacement NodeClaim + placements
 Everything computes behind the C ABI on the GPU; a missing libkp.so or HIP device raises.
 """
 import ctypes as C
@@ -121,6 +122,9 @@ def load_lib(path=None):
         "kp_cluster_drift": (C.c_int32, [C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32), C.c_uint32, P(C.c_uint32),
                                          C.c_uint32, P(abi.DriftResult), P(C.c_int64), P(C.c_void_p), P(C.c_uint64),
                                          P(abi.SolveStats)]),
+        "kp_cluster_command": (C.c_int32, [C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32), C.c_uint32, C.c_int32,
+                                           P(C.c_uint32), C.c_uint32, P(abi.SimResult), P(C.c_void_p), P(C.c_uint64),
+                                           P(abi.SolveStats)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name, None)
@@ -711,6 +715,40 @@ class ClusterPlan:
             results = [{f: int(getattr(out[i], f)) for f, _ in abi.DriftResult._fields_} for i in range(n)]
         return {"first": int(first.value), "replacements": repl, "results": results, "blocked": int(blocked.value),
                 "stats": stats_dict(st)}
+
+    def command(self, subsets, multi_node=True, allowed=None, cancel=None):
+        """kp_cluster_command: simulate() plus each decision's command. Returns (results, commands, stats): results as
+        simulate() gives them; commands[s] None for a no-op or a budget-blocked subset, else read_result of the command
+        (the dict form drift() uses for "replacements": no NodeClaim for a DELETE, one for a REPLACE whose options are
+        the ones the price filters kept; placements in the simulation's input order: pending, deleting nodes' pods, the
+        subset's pods); stats gain budget_blocked when allowed is given."""
+        lib = self.ctx.lib
+        arena = Arena()
+        offs, flat = abi.subsets_csr(arena, subsets)
+        n = len(subsets)
+        out = (abi.SimResult * max(1, n))()
+        cmds = (C.c_void_p * max(1, n))()
+        blocked, st = C.c_uint64(0), abi.SolveStats()
+        keep, ap, na = self._allowed(allowed) if allowed is not None else (None, None, 0)
+        _check(lib, lib.kp_cluster_command(self.h, cancel.h if cancel is not None else None, offs, flat, n,
+                                           1 if multi_node else 0, ap, na, out, cmds, C.byref(blocked), C.byref(st)))
+        commands = []
+        try:
+            cl = self.cluster
+            n_base = len(cl.pending) + sum(len(x.pods) for x in cl.nodes if x.deleting)
+            for s in range(n):
+                if not cmds[s]:
+                    commands.append(None)
+                    continue
+                commands.append(read_result(lib, C.c_void_p(cmds[s]), n_base + sum(len(cl.nodes[c].pods) for c in subsets[s])))
+        finally:
+            for s in range(n):
+                if cmds[s]:
+                    lib.kp_result_destroy(C.c_void_p(cmds[s]))
+        sd = stats_dict(st)
+        if allowed is not None:
+            sd["budget_blocked"] = int(blocked.value)
+        return [sim_dict(out[i]) for i in range(n)], commands, sd
 
     def close(self):
         if self.h:

@@ -325,7 +325,25 @@ class Controller:
     (the first candidate whose computeConsolidation is not a no-op). plan: the resident snapshot of `cluster`
     (ClusterPlan, or any object with the same simulate(subsets, multi_node)). When some NodePool has budgets, each
     method's candidates go through the budget walk first (Emptiness: reason Empty, the others: Underutilized); now,
-    not_ready and extra_deleting are allowed_disruptions' arguments."""
+    not_ready and extra_deleting are allowed_disruptions' arguments.
+
+    materialize=True: the multi-node and single-node winners are passed once more through plan.command([winner],
+    multi_node) (kp_cluster_command), and their Command.result gains "replacements" (the replacement NodeClaim, its
+    options the ones the price filters kept; none for a DELETE) and "placement" (where every rescheduled pod went) -
+    Drift's keys. The command call must decide what simulate decided. The default leaves plans without .command
+    working as before."""
+
+    def __init__(self, materialize=False):
+        self.materialize = materialize
+
+    def _materialized(self, plan, method, candidates, r):
+        if not self.materialize:
+            return Command(method, candidates, r["decision"], r)
+        res, cmds, _ = plan.command([list(candidates)], multi_node=method == "multi")
+        if res[0] != r or cmds[0] is None:
+            raise RuntimeError(f"command({candidates}) decided {res[0]}, simulate {r}")
+        out = dict(r, replacements=cmds[0]["nodeclaims"], placement=cmds[0]["placement"])
+        return Command(method, candidates, r["decision"], out)
 
     def compute_command(self, cluster, plan, now=None, not_ready=(), extra_deleting=None):
         cands = candidate_order(cluster)
@@ -343,11 +361,11 @@ class Controller:
         hit = multi.first_n_option(cands)
         if hit is not None:
             n, r = hit
-            return Command("multi", multi.candidates(cands)[:n], r["decision"], r)
+            return self._materialized(plan, "multi", multi.candidates(cands)[:n], r)
         hit = SingleNodeConsolidation(plan, cluster, allowed).compute_command(cands)
         if hit is not None:
             c, r = hit
-            return Command("single", [c], r["decision"], r)
+            return self._materialized(plan, "single", [c], r)
         return None
 
 
