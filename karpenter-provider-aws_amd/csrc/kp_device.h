@@ -115,7 +115,9 @@ struct SolveArgs {
   int32_t timing;                    // 1: thread 0 accumulates per-phase s_memtime deltas into stats[8..15]
   int32_t stop_nc;                   // > 0 (consolidation simulations): end the Solve once this many NodeClaims exist
   const int32_t* cancel;             // kp_cancel flag (host-mapped, polled every ~1024 pops), NULL: none
-  int32_t cont;                      // 1: the fast lane variant with the continuation round (queue runs of one shape)
+  int32_t cont;                      // the fast lane variant: 1 with the continuation round and the run-length commit
+                                     // (queue runs of one shape), 2 with the run-length commit alone (runs of shapes
+                                     // with one request row), 0 neither
   // topology spread (upstream Topology, TopologyTypeSpread groups). A group on a dictionary key keeps a
   // count per value ordinal and the mask of registered domains; a hostname group a saturating u8 count per
   // node (existing positions: hcnt_ex, NodeClaim ids: hcnt_nc).
@@ -191,6 +193,9 @@ struct SolveArgs {
   int32_t res_pad_;
   uint64_t res_cls;
   uint64_t* nc_held;                 // [P]
+  // [S] request class (the fast lane's run-length commit): equal iff the shapes' request rows are equal over all
+  // KP_NRES entries; a shape with host ports (shape_hp_conf != 0) has a class of its own
+  const int32_t* shape_rclass;
   int32_t res_cap0[KP_MAX_CLASSES];
 };
 

@@ -1315,11 +1315,13 @@ struct Compiled {
   vector<int64_t> tmpl_remaining;
   // shapes
   vector<int32_t> shape_level_base, shape_nlevels;
-  int32_t cont_hint = 0;  // most queue neighbours share their shape: the fast lane with its continuation round
+  int32_t cont_hint = 0;  // SolveArgs::cont: 1 most queue neighbours share their shape, 2 their request class
   vector<KReqs> shape_reqs;
   vector<uint64_t> shape_negop, shape_tolerates;  // per shape-level (tolerations change at the PreferNoSchedule level)
   vector<char> sl_pns;                             // per shape-level: toleratePreferNoScheduleTaints' level
   vector<int64_t> shape_requests;
+  vector<int32_t> shape_rclass;  // per shape: request class (SolveArgs::shape_rclass)
+  int32_t n_rclass = 0;          // ... and how many there are
   vector<uint64_t> pvp;
   vector<int32_t> pvp_base, pvp_slot, pvp_n;  // pvp_n: rows of catalogue 0 per shape-level
   // existing (sorted)
@@ -2820,6 +2822,24 @@ int32_t CompilePerCall(const kp_solve_in* in, const SolveRaw& raw, Compiled& cp)
     const int32_t hrc = EncodeHostPorts(hs, hn, cp);
     if (hrc) return hrc;
   }
+  {  // request classes: shapes with equal request rows share one (the run-length commit batches across them); a shape
+     // with host ports is handed to the full path pod by pod, so it gets a class nothing else has
+    std::map<vector<int64_t>, int32_t> cls;
+    cp.shape_rclass.assign(in->n_shapes, 0);
+    int32_t nc = 0;
+    for (uint32_t s2 = 0; s2 < in->n_shapes; s2++) {
+      if (cp.shape_hp_conf[s2]) {
+        cp.shape_rclass[s2] = nc++;
+        continue;
+      }
+      const vector<int64_t> row(cp.shape_requests.begin() + (size_t)s2 * KP_NRES,
+                                cp.shape_requests.begin() + (size_t)(s2 + 1) * KP_NRES);
+      auto it = cls.find(row);
+      if (it == cls.end()) it = cls.emplace(row, nc++).first;
+      cp.shape_rclass[s2] = it->second;
+    }
+    cp.n_rclass = nc;
+  }
   pt.lap(" host ports");
   int32_t rc = CompileTopology(in, cp, raw.strict_levels, raw.spread_levels, b.np_taintset, raw.filter_levels);
   if (rc) return rc;
@@ -2878,9 +2898,19 @@ int32_t CompilePerCall(const kp_solve_in* in, const SolveRaw& raw, Compiled& cp)
   for (uint32_t p = 0; p < in->n_pods; p++) cp.queue[p] = qk[p].pod;
   {  // the fast lane's continuation round pays where most queue neighbours share their shape (deployments created in
      // bursts: runs of one shape-level); elsewhere its registers cost more than it saves (measured)
-    uint32_t same = 0;
-    for (uint32_t p = 1; p < in->n_pods; p++) same += cp.pod_shape[cp.queue[p]] == cp.pod_shape[cp.queue[p - 1]];
-    cp.cont_hint = in->n_pods > 1 && 2 * same >= in->n_pods ? 1 : 0;
+    // Its run-length commit also takes neighbours of different shapes with one request row (the queue is sorted by
+    // cpu and memory, so shapes of one request class lie together): where most neighbours share their class and
+    // some class holds more than one shape, the batches outweigh the registers
+    uint32_t same = 0, same_rc = 0;
+    for (uint32_t p = 1; p < in->n_pods; p++) {
+      const int32_t s1 = cp.pod_shape[cp.queue[p]], s0 = cp.pod_shape[cp.queue[p - 1]];
+      same += s1 == s0;
+      same_rc += cp.shape_rclass[s1] == cp.shape_rclass[s0];
+    }
+    const bool runs = 2 * same >= in->n_pods;
+    const bool mixed_runs = 2 * same_rc >= in->n_pods && cp.n_rclass < (int32_t)in->n_shapes;
+    // (2: the run-length commit without the continuation round, which only pays inside runs of one shape)
+    cp.cont_hint = in->n_pods <= 1 ? 0 : runs ? 1 : mixed_runs ? 2 : 0;
   }
   pt.lap(" queue");
   return KP_OK;
@@ -3078,7 +3108,7 @@ struct SolveOffs {
          exts = 0, exav = 0, shpc = 0, shpa = 0, tgk = 0, tgr = 0, tgs = 0, tgm = 0, tga = 0, tgtb = 0, tgft = 0,
          tgt = 0, tgtn = 0, tgnt = 0, srb = 0, srn = 0, recl = 0, recx = 0, slft = 0, slob = 0, slon = 0, owng = 0,
          owns = 0, ownp = 0, ownr = 0, sltk = 0, tks = 0, extc = 0, tkk = 0, slsh = 0, tfeas = 0, exul = 0, exuo = 0,
-         exui = 0, slst = 0;
+         exui = 0, slst = 0, srcl = 0;
   // arena: the Solve's inputs, then its mutable state [mut, mut_end) (restored before every run; [mut, common) is the
   // part a batched simulation patches, [common, mut_end) the part every simulation starts from alike), then
   // device-only regions
@@ -3171,6 +3201,7 @@ void PutShared(Blob& blob, const Compiled& C, SolveOffs& o) {
   o.exav = blob.put(C.ex_available);
   o.shpc = blob.put(C.shape_hp_conf);
   o.shpa = blob.put(C.shape_hp_add);
+  o.srcl = blob.put(C.shape_rclass);
   // topology (read-only part)
   o.tgk = blob.put(C.tg_key), o.tgr = blob.put(C.tg_row), o.tgs = blob.put(C.tg_maxskew), o.tgm = blob.put(C.tg_mindom);
   o.tga = blob.put(C.tg_aff), o.tgtb = blob.put(C.tg_term_base), o.tgft = blob.put(C.tg_filt_tol);
@@ -3353,6 +3384,7 @@ void BindSolve(SolveArgs& a, const Compiled& C, const SolveOffs& o, uint8_t* sh,
   a.hp_any = C.hp_any ? 1 : 0;
   a.shape_hp_conf = (const uint64_t*)(sh + o.shpc);
   a.shape_hp_add = (const uint64_t*)(sh + o.shpa);
+  a.shape_rclass = (const int32_t*)(sh + o.srcl);
   a.ex_hp = (uint64_t*)(ar + o.exhp);
   a.nc_hp = (uint64_t*)(ar + o.nchp);
   a.req_res_mask = rmask;

@@ -1654,6 +1654,23 @@ __device__ __forceinline__ void mstack_push_reg(int32_t LDS* stk, int& n, int& l
   wave_sync();
 }
 
+// The time of the newest stack entry at a position below pos (`lost` when there is none): a cursor stamped at or after
+// it has seen every mutation below pos, so its query answers >= pos. The entries at >= pos are a suffix (what
+// mstack_push_reg would pop for pos), found the same way; the stack is left as it is.
+__device__ __forceinline__ int mstack_time_below(const int32_t LDS* stk, int n, int lost, int pos) {
+  const int lane = LANE;
+  for (;;) {
+    const int base = max(0, n - 64);
+    const int j = base + lane;
+    const int pv = stk[2 * min(j, MSTK_CAP - 1) + 1];
+    const uint64_t ge = __ballot(j < n && pv >= pos);
+    if (!ge) break;
+    n = base + __builtin_ctzll(ge);
+    if (n > base || base == 0) break;
+  }
+  return n > 0 ? stk[2 * (n - 1)] : lost;
+}
+
 // ---- the spilled newNodeClaims order as chunks ------------------------------------------------------------------
 // Past the LDS sort capacity the sorted order is a sequence of chunks of at most 64 NodeClaims: one global block per
 // chunk (ids and len(Pods) in order, ChkBlk), and a directory in LDS (the LDS sort arrays' space): per chunk its block,
@@ -2120,6 +2137,10 @@ struct FastState {
   uint64_t bytes, attempts, scanned, starts, fpods, runpods;
   uint64_t fcyc[16];  // [0..5] phases; [6..13] finer probes (FT_FINE builds, exported in place of stats[16..23])
   uint32_t fbail[8];
+  // the continuation variant's run-length commit: per window entry its shape's request class and its level's
+  // tolerations (static while the entry waits, like the rest of the window; in LDS, not in the loop's registers)
+  int32_t qw_rc[64];
+  uint64_t qw_tol[64];
 };
 __shared__ FastState g_fast;
 
@@ -2193,7 +2214,9 @@ __device__ __forceinline__ T ka_read(uint32_t k0, uint32_t k1, uint32_t k2, uint
 // directory in s_dyn, see chk_sort): the replay edits the blocks and the scan walks the live chunks, one per round.
 // EX: the Solve has existing nodes (addToExistingNode on the wave); without, that code is compiled out, so it costs
 // the Solves without existing nodes no registers (measured: 9 % of config 2's kernel when only skipped at run time).
-template <bool TOPO, bool CHK, bool EX, bool CONT>
+// CONT: 0 none; 1 the continuation round and the run-length commit; 2 the run-length commit alone (on config 2 the
+// round costs 3 % of the kernel and saves nothing once the commit takes the runs: 181.6 against 175.9 ms, measured).
+template <bool TOPO, bool CHK, bool EX, int CONT>
 __device__ __noinline__ int fast_lane(uint64_t kargs, int32_t LDS* s_dyn_arg, uint64_t pops_in_arg) {
   // a callee's arguments arrive in VGPRs and count as divergent: made provably uniform here, or every value and
   // branch that depends on them (the whole pod loop) would be compiled as divergent control flow
@@ -2349,6 +2372,13 @@ if (!FL_NOTIME && tmg) {                                    \
         READY(qw_sl);
         READY(qw_lastlen);
         READY(qw_epoch);
+        if (CONT) {  // (reads at valid indices on every lane: the lanes past the window read entry 0, unused)
+          const int32_t rc_r = KA(shape_rclass)[lane < qw_n ? qw_shape : 0];
+          const uint64_t tol_r = KA(shape_tolerates)[lane < qw_n ? qw_sl : 0];
+          S->qw_rc[lane] = rc_r;
+          S->qw_tol[lane] = tol_r;
+          wave_sync();
+        }
       }
       qw_next = off + 1;  // only the fast lane pops: the next pop reads the following entry
       const int pod = __builtin_amdgcn_readlane(qw_pod, off);
@@ -2792,7 +2822,7 @@ if (!FL_NOTIME && tmg) {                                    \
       // unchanged): the first candidate is c_nc itself, whose pre-check record, remaining types, requests and
       // threshold indices the wave holds from that commit — no gathers for this round (c_nc is tagged with the
       // level: memo NC_MERGED). A failed attempt falls back to the scan from the next position.
-      bool cont = CONT && FAST_CONT && !CHK && !TOPO && c_nc >= 0 && cont_w >= 0 && cont_w == start &&
+      bool cont = CONT == 1 && FAST_CONT && !CHK && !TOPO && c_nc >= 0 && cont_w >= 0 && cont_w == start &&
                   mut_was1 && !n_moved && sl == cont_sl && rr_b4p == 0 && c_hm == 0;
       bool bail = !CHK && n_nc - start > FAST_SCAN_MAX && !cont;
       if (bail) why = FB_SCAN;
@@ -3143,30 +3173,73 @@ if (!FL_NOTIME && tmg) {                                    \
       // remaining types, and so the result, unchanged). k is the largest count for which all of that holds in
       // closed form; the k pods are committed at once: requests + k * pod, len(Pods) + k, headroom - k * pod, version
       // + k, the same cursor and one mutation-stack entry for the k identical ones. Anything else: the pod loop.
+      //
+      // Mixed runs: none of that needs the entries to share this pod's level. The queue is sorted by (cpu, memory), so
+      // long stretches of it carry one request row and differ only in requirements; an entry of another level e is
+      // accepted when the pod loop would still take exactly the same steps for it, each of which is a check the loop
+      // makes itself, at state the batch leaves as it is for the next entry:
+      //  - the same request row and fast-lane eligible: one request class (SolveArgs::shape_rclass; a shape with host
+      //    ports has a class of its own, so it ends the run). Fits and the headroom pre-check then see the same numbers;
+      //  - its level is merged into this NodeClaim (nc_fail >= NC_MERGED, the loop's `tag`) and tolerates its taint set,
+      //    so the first candidate at wpos is this NodeClaim on the append path (no minValues: c_hm == 0). A commit
+      //    changes neither (nc_fail rows of other levels are untouched by an append);
+      //  - its scan starts exactly at wpos: start = min(cursor position, lowest position mutated since the cursor's
+      //    stamp, the replayed mutation's position wpos). The mutation stack is monotone (time and position increase
+      //    bottom to top), so after popping what lies at >= wpos its top is the newest mutation below wpos, at time
+      //    t_below: the start is wpos iff cursor position >= wpos and stamp >= t_below (>= the lost time when nothing
+      //    lies below). The batch pushes at wpos only, so the test holds for every later entry as evaluated now, and
+      //    a level's later occurrences read the cursor (wpos, now) its first one stored, which passes.
+      // Each accepted entry's level gets the cursor (wpos, stk_t) the loop would have stored for it (the stamps of
+      // the earlier ones differ from the loop's by pushes at wpos alone, which no query can tell apart).
       if (CONT && cont_w == wpos && c_cat == 0 && c_hm == 0 && rr_b4p == 0 && n_rrp <= 4) {
         const int e = off + 1 + lane;  // lane j: the j-th window entry after this pod
         const int e_sl = __shfl(qw_sl, e & 63, 64), e_ep = __shfl(qw_epoch, e & 63, 64),
                   e_ll = __shfl(qw_lastlen, e & 63, 64), e_pod = __shfl(qw_pod, e & 63, 64);
+        const int e_rc = S->qw_rc[e & 63], rc = U(S->qw_rc[off]);  // request classes (filled with the window)
         // Queue.Pop would stop at an entry last pushed at the length it would pop it at (lastLen)
-        const bool ok = e < qw_n && e_sl == sl && !(e_ep == epoch && e_ll == q_len - lane);
+        const bool ok = e < qw_n && e_rc == rc && !(e_ep == epoch && e_ll == q_len - lane);
         const uint64_t okm = __ballot(ok);
         int k = (int)__builtin_ctzll(~okm);
-        // sort.Slice: batched pod m (1-based) replays len(Pods) = c + m - 1 at wpos against the next entry's
-        const int c1 = npods[placed];
-        const int nxt = wpos + 1 < n_nc_all ? npods[ord[wpos + 1]] : INT32_MAX;
-        if (nxt != INT32_MAX) k = min(k, max(0, nxt - c1 + 1));
-        // Fits: every requested resource stays at or under the threshold value of its current index
-        int kf = INT32_MAX;
-        if (lane < KP_NRES && preq_lane > 0) {
-          const int slot = g_hdr[0].fit_slot[lane], n = g_hdr[0].fit_n[lane];
-          kf = 0;
-          if (slot >= 0 && c_fj < n) {
-            const int64_t room = g_fitv[slot * FITV_CAP + c_fj] - c_q;
-            kf = room >= 0 ? (int)min<int64_t>(room / preq_lane, 64) : 0;
-          }
+        int c1 = 0;
+        if (k > 0) {  // (uniform: the rest is skipped when the next entry already fails the register checks)
+          // sort.Slice: batched pod m (1-based) replays len(Pods) = c + m - 1 at wpos against the next entry's
+          c1 = npods[placed];
+          const int nxt = wpos + 1 < n_nc_all ? npods[ord[wpos + 1]] : INT32_MAX;
+          if (nxt != INT32_MAX) k = min(k, max(0, nxt - c1 + 1));
+          // Fits: every resource the pod requests stays at or under the threshold value of its current index. Lane r
+          // holds resource r's room under that value (-1: no staged value to compare with); lane j then tests j + 1
+          // more pods against each requested resource's room (no division: the requested ones are the first four)
+          const int rl = min(lane, KP_NRES - 1);
+          const int slot = g_hdr[0].fit_slot[rl], n = g_hdr[0].fit_n[rl];
+          const bool has = lane < KP_NRES && slot >= 0 && c_fj < n;
+          const int64_t thr = g_fitv[has ? slot * FITV_CAP + c_fj : 0];  // (read at a valid index, masked after)
+          const int64_t room = has ? thr - c_q : -1;
+          bool fitk = true;
+#pragma unroll
+          for (int i = 0; i < 4; i++)
+            if (i < n_rrp) {
+              const int r = (rrp >> (8 * i)) & 0xff;
+              const int64_t p_r = lane_bcast_i64(preq_lane, r), room_r = lane_bcast_i64(room, r);
+              fitk = fitk & (p_r <= 0 || (int64_t)(lane + 1) * p_r <= room_r);
+            }
+          const uint64_t nfm = ~__ballot(fitk);
+          k = min(k, nfm ? (int)__builtin_ctzll(nfm) : 64);
+          k = min(k, 63);
         }
-        k = min(k, wave_min_i32(kf));
-        k = min(k, 63);
+        // entries of another level among the first k: merged into this NodeClaim, tolerated, scan starting at wpos
+        // (one gather round, paid only by runs that have such an entry; uniform branch)
+        if (k > 0 && __ballot(lane < k && e_sl != sl)) {
+          const int t_floor = mstack_time_below((LdsI32)s_stk[0], stk_n, stk_lost, wpos);
+          const int ncc_ = KA(ncc);
+          const int g_sl = lane < k ? e_sl : sl;  // (gathers at valid indices, masked after)
+          const int32_t fl_e = KA(nc_fail)[(size_t)g_sl * ncc_ + min(placed, ncc_ - 1)];
+          const int2 cu_e = *reinterpret_cast<const int2*>(&KA(cur_nc)[2 * g_sl]);
+          const uint64_t tol_e = S->qw_tol[e & 63];
+          const bool ok2 = e_sl == sl || (placed < ncc_ && fl_e >= NC_MERGED && ((tol_e >> c_ts) & 1) != 0 &&
+                                          cu_e.x >= wpos && cu_e.y >= t_floor);
+          const uint64_t bad = ~__ballot(ok2) & ((1ull << k) - 1);
+          if (bad) k = __builtin_ctzll(bad);
+        }
         if (k > 0) {
           const int64_t kk = k;
           // the NodeClaim: requests, len(Pods), pre-check record (headroom, version)
@@ -3189,7 +3262,11 @@ if (!FL_NOTIME && tmg) {                                    \
           stk_t += k;
           mstack_push_reg((int32_t LDS*)s_stk[0], stk_n, stk_lost, stk_t, wpos);
           a_cur_prev_stamp = stk_t;
-          *reinterpret_cast<int2*>(&KA(cur_nc)[2 * sl]) = make_int2(wpos, stk_t);
+          // (lane j: the j-th entry's level; duplicate levels write equal values, and the lanes past k repeat the last
+          // entry's, so every lane stores)
+          cont_sl = __builtin_amdgcn_readlane(e_sl, k - 1);
+          prev_sl = -1;  // (the next pod's level may be one whose cursor the register shortcut does not hold)
+          *reinterpret_cast<int2*>(&KA(cur_nc)[2 * (lane < k ? e_sl : cont_sl)]) = make_int2(wpos, stk_t);
           // the k pods: popped, placed (events in queue order after the buffered ones)
           if (n_buf + k > 64) {
             if (lane < n_buf) {
@@ -3422,18 +3499,21 @@ __global__ __launch_bounds__(NW * 64) void solve_kernel(SolveArgs a0, const Solv
       } else {
         // the Solve's argument block: the kernarg segment (a0 is the first argument), or its entry of the batch
         const uint64_t kargs = BATCH ? (uint64_t)&batch[blockIdx.x] : (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
-        // instantiations: chunked order or not, existing nodes or none (compiled out), the continuation round (LDS
-        // order, no topology, queue runs of one shape)
+        // instantiations: chunked order or not, existing nodes or none (compiled out), and for the LDS order without
+        // topology the run-length commit, with the continuation round (cont 1: queue runs of one shape) or without it
+        // (cont 2: runs of shapes with one request row, where the round's registers cost more than it saves)
         int placed_fast;
         if (s_ctl[5] == 2)
-          placed_fast = a.n_existing ? fast_lane<TOPO, true, true, false>(kargs, (int32_t LDS*)s_dyn, pops)
-                                     : fast_lane<TOPO, true, false, false>(kargs, (int32_t LDS*)s_dyn, pops);
+          placed_fast = a.n_existing ? fast_lane<TOPO, true, true, 0>(kargs, (int32_t LDS*)s_dyn, pops)
+                                     : fast_lane<TOPO, true, false, 0>(kargs, (int32_t LDS*)s_dyn, pops);
         else if (a.n_existing)
-          placed_fast = fast_lane<TOPO, false, true, false>(kargs, (int32_t LDS*)s_dyn, pops);
+          placed_fast = fast_lane<TOPO, false, true, 0>(kargs, (int32_t LDS*)s_dyn, pops);
+        else if (!TOPO && a.cont == 2)
+          placed_fast = fast_lane<TOPO, false, false, TOPO ? 0 : 2>(kargs, (int32_t LDS*)s_dyn, pops);
         else if (!TOPO && a.cont)
-          placed_fast = fast_lane<TOPO, false, false, !TOPO>(kargs, (int32_t LDS*)s_dyn, pops);
+          placed_fast = fast_lane<TOPO, false, false, TOPO ? 0 : 1>(kargs, (int32_t LDS*)s_dyn, pops);
         else
-          placed_fast = fast_lane<TOPO, false, false, false>(kargs, (int32_t LDS*)s_dyn, pops);
+          placed_fast = fast_lane<TOPO, false, false, 0>(kargs, (int32_t LDS*)s_dyn, pops);
         pops += placed_fast;
         fl_fail = placed_fast ? 0 : fl_fail + 1;
         fl_skip = fl_fail >= 2 ? min(1 << min(fl_fail - 2, 6), 64) : 0;
