@@ -433,7 +433,10 @@ int32_t kp_ctx_create(const kp_options* opts, kp_ctx** out);
  * the plan was prepared: setting them takes effect on the next call on any existing plan. */
 typedef struct kp_overrides {
   int32_t fast_lane;           /* 0 auto (the run-length-commit variant where most queue neighbours share their shape),
-                                  1 the plain variant, 2 the run-length-commit variant */
+                                  1 the plain variant, 2 the run-length-commit variant with the continuation round,
+                                  3 the run-length-commit variant without it (the one auto picks for queue runs of
+                                  different shapes with one request row). Solves for which 2 or 3 is not built
+                                  (topology, existing nodes, a spilled order) run the plain variant */
   int32_t sort_capacity;       /* 0: 8192 NodeClaims in the LDS order; n > 0: the chunked order past n NodeClaims */
   int32_t chunk_capacity;      /* 0: the chunked order's full directory; n > 0: at most n chunks (then the flat order);
                                   n < 0: no chunks (the flat order past sort_capacity) */

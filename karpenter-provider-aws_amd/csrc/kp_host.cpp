@@ -3390,7 +3390,10 @@ void BindSolve(SolveArgs& a, const Compiled& C, const SolveOffs& o, uint8_t* sh,
   a.req_res_mask = rmask;
   a.n_req_res = __builtin_popcount(rmask);
   a.timing = C.ov.timing ? 1 : 0;
-  a.cont = C.ov.fast_lane ? (C.ov.fast_lane == 2 ? 1 : 0) : C.cont_hint;
+  // kp_overrides.fast_lane: 1 plain, 2 cont 1, 3 cont 2. solve_kernel's dispatch takes a forced value as it takes the
+  // hint: cont 1 and cont 2 are instantiated for the LDS order without topology and without existing nodes only, and
+  // every other Solve (topology, existing nodes, the chunked or flat order from the spill on) runs CONT 0
+  a.cont = C.ov.fast_lane ? (C.ov.fast_lane == 2 ? 1 : C.ov.fast_lane == 3 ? 2 : 0) : C.cont_hint;
   a.n_groups = C.G;
   a.tg_key = (const int32_t*)(sh + o.tgk);
   a.tg_row = (const int32_t*)(sh + o.tgr);

@@ -1,6 +1,6 @@
 """The fast lane's run-length commit. In Solves whose queue runs of one shape-level
 are the rule (deployments created in bursts: kp_solve picks the continuation variant when most queue neighbours share
-their shape; kp_overrides.fast_lane forces either variant), the fast lane commits the next k pods of a run onto the NodeClaim the run
+their shape; kp_overrides.fast_lane forces any variant), the fast lane commits the next k pods of a run onto the NodeClaim the run
 is filling in one step when, for each of them one at a time, the reference would do the same: sort.Slice leaves the
 NodeClaim in place (the next entry's len(Pods) is not below its own), the first-fit scan starts at it, and Fits over
 its remaining types holds with every requested resource under the threshold value it last passed. Parity: device ==
@@ -10,8 +10,9 @@ import pytest
 
 
 def _solve(ctx, prob, cont, ov):
+    """cont: False plain, True the run-length commit with the continuation round, 3 the commit without it."""
     import kpamd
-    ov(fast_lane=2 if cont else 1)
+    ov(fast_lane=3 if cont == 3 else 2 if cont else 1)
     return kpamd.Scheduler(ctx, prob).solve()
 
 
@@ -32,14 +33,16 @@ def test_burst_run_length_equals_oracle(ctx, catalog, ov, n_pods, seed):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("seed", range(6))
-def test_forced_run_length_on_random_problems(ctx, catalog, ov, seed):
+@pytest.mark.parametrize("seed,n_catalogs", [(s, c) for c in (1, 3) for s in range(6)],
+                         ids=[str(s) if c == 1 else f"{s}-{c}catalogues" for c in (1, 3) for s in range(6)])
+def test_forced_run_length_on_random_problems(ctx, catalog, ov, seed, n_catalogs):
     """Limits, taints, minValues, relaxations (re-queued pods: lastLen), several catalogues: the continuation variant
     forced on equals the oracle."""
     from kpamd import synth
     from oracle import pyoracle
     from test_gpu_parity import check_same
-    prob = synth.random_problem(catalog, 1600 + seed, n_types=150, n_pods=600, n_pools=3, n_shapes=6)
+    prob = synth.random_problem(catalog, 1600 + seed, n_types=150, n_pods=600, n_pools=3, n_shapes=6,
+                                n_catalogs=n_catalogs)
     check_same(_solve(ctx, prob, True, ov), pyoracle.solve(prob))
 
 
@@ -62,6 +65,7 @@ def test_run_cut_by_thresholds_and_ties(ctx, catalog, ov):
     uid = np.arange(1, len(blocks) + 1, dtype=np.uint64)
     prob = Problem([catalog], [pool], shapes, shape, creation, uid, name="run-cuts")
     want = pyoracle.solve(prob)
-    got = _solve(ctx, prob, True, ov)
-    check_same(got, want)
-    assert got["stats"]["run_length_pods"] > 0
+    for cont in (True, 3):
+        got = _solve(ctx, prob, cont, ov)
+        check_same(got, want)
+        assert got["stats"]["run_length_pods"] > 0

@@ -4,7 +4,8 @@ them onto the NodeClaim it is filling in one step when each is of the same reque
 level is already merged into that NodeClaim and tolerates its taints, its first-fit scan starts exactly there (cursor
 and mutation stack), sort.Slice leaves the NodeClaim in place and Fits holds in closed form. Parity: device == the
 one-pod-at-a-time oracle on crafted queues where each of those conditions cuts runs, under the default overrides
-(kp_solve picks the variant from the queue) and with the batching forced off; the stats count the batched pods."""
+(kp_solve picks the variant from the queue), with either run-length variant forced (kp_overrides.fast_lane 2: with the
+continuation round, 3: without) and with the batching forced off; the stats count the batched pods."""
 import numpy as np
 import pytest
 
@@ -23,7 +24,8 @@ def _problem(catalog, pools, shapes, order, name):
 
 
 def _both(ctx, ov, prob, expect_runs=True):
-    """Default overrides and forced plain against the oracle; returns (default result, oracle result)."""
+    """Default overrides, both forced run-length variants and forced plain against the oracle; returns (default
+    result, oracle result)."""
     import kpamd
     from oracle import pyoracle
     from test_gpu_parity import check_same
@@ -34,6 +36,13 @@ def _both(ctx, ov, prob, expect_runs=True):
     print(prob.name, "run_length_pods", got["stats"]["run_length_pods"], "of", len(prob.pod_shape))
     if expect_runs:
         assert got["stats"]["run_length_pods"] > 0
+    for forced in (2, 3):
+        ov(fast_lane=forced)
+        on = kpamd.Scheduler(ctx, prob).solve()
+        check_same(on, want)
+        print(prob.name, "fast_lane", forced, "run_length_pods", on["stats"]["run_length_pods"])
+        if expect_runs:
+            assert on["stats"]["run_length_pods"] > 0
     ov(fast_lane=1)
     off = kpamd.Scheduler(ctx, prob).solve()
     check_same(off, want)
@@ -85,8 +94,9 @@ def test_cursor_both_ways(ctx, catalog, ov, every, third_first):
         else:
             order.append(j % 2)
             j += 1
+    # (third shape in every 5th or 7th slot only: runs of the other two, merged into the shared NodeClaim, lie between)
     _both(ctx, ov, _problem(catalog, [_pool()], [a, b, c], order, f"mixed-cursor-{every}-{int(third_first)}"),
-          expect_runs=False)
+          expect_runs=not third_first and every in (5, 7))
 
 
 @pytest.mark.gpu
