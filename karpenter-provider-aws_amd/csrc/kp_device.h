@@ -190,12 +190,20 @@ struct SolveArgs {
   // 2 strict. A reservation id is one offering class (res_cls); its remaining capacity lives in LDS during the Solve,
   // starting from res_cap0; nc_held[nc] = the classes NodeClaim nc holds (zeroed per run)
   int32_t res_mode;
-  int32_t res_pad_;
+  int32_t rqc_empty;                 // requirement class of the empty requirement set (see sl_rqc), -1: none
   uint64_t res_cls;
   uint64_t* nc_held;                 // [P]
   // [S] request class (the fast lane's run-length commit): equal iff the shapes' request rows are equal over all
   // KP_NRES entries; a shape with host ports (shape_hp_conf != 0) has a class of its own
   const int32_t* shape_rclass;
+  // requirement classes: sl_rqc[sl] = the class of shape-level sl, equal iff the levels' compiled requirements (KReqs
+  // bytes, negop, PVP rows) are equal; the members of class c are rqc_mem[rqc_off[c] .. rqc_off[c + 1]). Intersecting a
+  // requirement set into a NodeClaim a second time changes nothing, so a merge of one member tags every member merged
+  // on that NodeClaim (nc_fail NC_MERGED), and a permanent failure of Compatible fails every member (NC_NEVER). A
+  // shape with host ports, and every level of a Solve with topology groups, is a class of its own.
+  const int32_t* sl_rqc;             // [SL]
+  const int32_t* rqc_off;            // [classes + 1]
+  const int32_t* rqc_mem;            // [SL]
   int32_t res_cap0[KP_MAX_CLASSES];
 };
 

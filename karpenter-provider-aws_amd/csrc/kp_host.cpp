@@ -1322,6 +1322,10 @@ struct Compiled {
   vector<int64_t> shape_requests;
   vector<int32_t> shape_rclass;  // per shape: request class (SolveArgs::shape_rclass)
   int32_t n_rclass = 0;          // ... and how many there are
+  // requirement classes (SolveArgs::sl_rqc): class per shape-level, CSR of each class's member levels, and the class
+  // of the empty requirement set (-1: none)
+  vector<int32_t> sl_rqc, rqc_off, rqc_mem;
+  int32_t rqc_empty = -1;
   vector<uint64_t> pvp;
   vector<int32_t> pvp_base, pvp_slot, pvp_n;  // pvp_n: rows of catalogue 0 per shape-level
   // existing (sorted)
@@ -2844,6 +2848,42 @@ int32_t CompilePerCall(const kp_solve_in* in, const SolveRaw& raw, Compiled& cp)
   int32_t rc = CompileTopology(in, cp, raw.strict_levels, raw.spread_levels, b.np_taintset, raw.filter_levels);
   if (rc) return rc;
   pt.lap(" topology");
+  {  // requirement classes: shape-levels whose compiled requirements (and so their negop and PVP rows) are equal share
+     // one. Requirement.Intersection is idempotent, so once one member is merged into a NodeClaim, NodeClaim.Add of
+     // every other member is Fits alone there: the device tags the whole class merged (SolveArgs::sl_rqc). A shape
+     // with host ports is handed to the full path pod by pod and keeps a class of its own; with topology groups a
+     // merge also narrows by the counts, so every level is its own class there
+    const size_t SLn = cp.shape_reqs.size();
+    std::map<string, int32_t> cls;
+    cp.sl_rqc.assign(SLn, 0);
+    cp.rqc_empty = -1;
+    int32_t nc = 0;
+    string key;
+    for (uint32_t s2 = 0; s2 < in->n_shapes; s2++)
+      for (int l = 0; l < cp.shape_nlevels[s2]; l++) {
+        const size_t sl2 = (size_t)cp.shape_level_base[s2] + l;
+        if (cp.G > 0 || cp.shape_hp_conf[s2]) {
+          cp.sl_rqc[sl2] = nc++;
+          continue;
+        }
+        key.assign(reinterpret_cast<const char*>(&cp.shape_reqs[sl2]), sizeof(KReqs));
+        key.append(reinterpret_cast<const char*>(&cp.shape_negop[sl2]), sizeof(uint64_t));
+        key.append(reinterpret_cast<const char*>(&cp.pvp_n[sl2]), sizeof(int32_t));
+        auto it = cls.find(key);
+        if (it == cls.end()) {
+          it = cls.emplace(key, nc++).first;
+          if (cp.shape_reqs[sl2].present == 0) cp.rqc_empty = it->second;
+        }
+        cp.sl_rqc[sl2] = it->second;
+      }
+    cp.rqc_off.assign((size_t)nc + 1, 0);
+    for (size_t i = 0; i < SLn; i++) cp.rqc_off[(size_t)cp.sl_rqc[i] + 1]++;
+    for (int32_t c = 0; c < nc; c++) cp.rqc_off[(size_t)c + 1] += cp.rqc_off[c];
+    cp.rqc_mem.assign(std::max<size_t>(1, SLn), 0);
+    vector<int32_t> fill(cp.rqc_off.begin(), cp.rqc_off.end() - 1);
+    for (size_t i = 0; i < SLn; i++) cp.rqc_mem[fill[cp.sl_rqc[i]]++] = (int32_t)i;
+  }
+  pt.lap(" requirement classes");
   // pods: Queue order byCPUAndMemoryDescending (cpu desc, memory desc, creation asc, uid asc)
   cp.pod_shape.resize(in->n_pods);
   cp.queue.resize(in->n_pods);
@@ -3108,7 +3148,7 @@ struct SolveOffs {
          exts = 0, exav = 0, shpc = 0, shpa = 0, tgk = 0, tgr = 0, tgs = 0, tgm = 0, tga = 0, tgtb = 0, tgft = 0,
          tgt = 0, tgtn = 0, tgnt = 0, srb = 0, srn = 0, recl = 0, recx = 0, slft = 0, slob = 0, slon = 0, owng = 0,
          owns = 0, ownp = 0, ownr = 0, sltk = 0, tks = 0, extc = 0, tkk = 0, slsh = 0, tfeas = 0, exul = 0, exuo = 0,
-         exui = 0, slst = 0, srcl = 0;
+         exui = 0, slst = 0, srcl = 0, rqcs = 0, rqco = 0, rqcm = 0;
   // arena: the Solve's inputs, then its mutable state [mut, mut_end) (restored before every run; [mut, common) is the
   // part a batched simulation patches, [common, mut_end) the part every simulation starts from alike), then
   // device-only regions
@@ -3202,6 +3242,7 @@ void PutShared(Blob& blob, const Compiled& C, SolveOffs& o) {
   o.shpc = blob.put(C.shape_hp_conf);
   o.shpa = blob.put(C.shape_hp_add);
   o.srcl = blob.put(C.shape_rclass);
+  o.rqcs = blob.put(C.sl_rqc), o.rqco = blob.put(C.rqc_off), o.rqcm = blob.put(C.rqc_mem);
   // topology (read-only part)
   o.tgk = blob.put(C.tg_key), o.tgr = blob.put(C.tg_row), o.tgs = blob.put(C.tg_maxskew), o.tgm = blob.put(C.tg_mindom);
   o.tga = blob.put(C.tg_aff), o.tgtb = blob.put(C.tg_term_base), o.tgft = blob.put(C.tg_filt_tol);
@@ -3385,6 +3426,10 @@ void BindSolve(SolveArgs& a, const Compiled& C, const SolveOffs& o, uint8_t* sh,
   a.shape_hp_conf = (const uint64_t*)(sh + o.shpc);
   a.shape_hp_add = (const uint64_t*)(sh + o.shpa);
   a.shape_rclass = (const int32_t*)(sh + o.srcl);
+  a.sl_rqc = (const int32_t*)(sh + o.rqcs);
+  a.rqc_off = (const int32_t*)(sh + o.rqco);
+  a.rqc_mem = (const int32_t*)(sh + o.rqcm);
+  a.rqc_empty = C.rqc_empty;
   a.ex_hp = (uint64_t*)(ar + o.exhp);
   a.nc_hp = (uint64_t*)(ar + o.nchp);
   a.req_res_mask = rmask;

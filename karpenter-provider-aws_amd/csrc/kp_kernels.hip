@@ -36,6 +36,7 @@
 #if !defined(KP_DIAG_BUILD) &&                                                                                       \
     (defined(FASTLANE) || defined(FL_NOTIME) || defined(FT_FINE) || defined(FAST_SCAN_MAX) ||                        \
      defined(FAST_CHK_LIVE) || defined(FAST_EX_ROUNDS) || defined(FAST_CONT) || defined(SORT_DIAG) || defined(EX_DIAG) || defined(FX_DIAG) || defined(FEAS_MAX_BLOCKS) ||                 \
+     defined(REQ_CLASSES) || defined(MERGE_DIAG) ||                 \
      defined(FEASQ_EW) || defined(FEASQ_ROWS) || defined(FEASQ_B128) || defined(FEASQ_SKIP_EVAL) || defined(FL_SKIP) ||  \
      defined(SIM_WPE) || defined(FEASQ_MINW))
 #error "a measurement knob is set outside a tools/ variant build (tools/kp_diag.h)"
@@ -65,6 +66,9 @@
 #ifndef FAST_CONT
 #define FAST_CONT 1  // the continuation round (the previous pod's NodeClaim tested from registers first)
 #endif
+#ifndef REQ_CLASSES
+#define REQ_CLASSES 3  // a merge, or a permanent failure of Compatible, is memoised for the level's whole requirement class
+#endif                 // (SolveArgs::sl_rqc): bit 0 by the fast lane's writers, bit 1 by the full path's; 0: for the level alone
 #ifndef FL_SKIP
 #define FL_SKIP 0  // diagnostic cost attribution, WRONG PLACEMENTS: bit 0 no sort replay, bit 1 no mutation stack
 #endif             // (cursor as stored), bit 2 no statistics counters
@@ -1322,6 +1326,9 @@ __device__ void slow_sort_wave(P ord, P npods, int n) {
 #ifndef EX_DIAG
 #define EX_DIAG 0  // diagnostic: the existing-node scan (range, scanned, cursor clamp, scans, cycles, placed) in stats[25..30]
 #endif
+#ifndef MERGE_DIAG
+#define MERGE_DIAG 0  // diagnostic (FT_FINE builds): the fast lane's attempt interval FTF(11) split into merges, failed full adds and appends (count, cycles each) in stats[25..30]
+#endif
 #ifndef FX_DIAG
 #define FX_DIAG 0  // diagnostic: the fast lane's existing-node scans (scans, rounds, placed, skipped, failed, bailed) in stats[25..30]
 #endif
@@ -2166,6 +2173,38 @@ __device__ __noinline__ uint64_t fl_fits_filter(int cat_a, uint64_t X0, int64_t 
   if (LANE == 0) fl_io[1] = nb;
   wave_sync();
   return X;
+}
+
+// The memo of one NodeClaim (col = nc_fail + its id, rows ncc apart) for every member level of requirement class c
+// (SolveArgs::sl_rqc), one member per lane: NC_MERGED after a merge of one member (Requirement.Intersection is
+// idempotent: Add of every other member is then Fits alone), NC_NEVER after a permanent failure of Compatible (a
+// property of the requirement set). A merge leaves a member's NC_NEVER as it is: that is a Fits failure of a level
+// with larger requests, which stays that level's own.
+__device__ __forceinline__ void rqc_spread(int32_t* col, int ncc, const int32_t* off, const int32_t* mem, int c, int32_t val) {
+  const int hi = off[c + 1];
+  for (int i = off[c] + LANE; i < hi; i += 64) {
+    int32_t* p = col + (size_t)mem[i] * ncc;
+    if (val != NC_MERGED || *p != NC_NEVER) *p = val;
+  }
+}
+// The fast lane's, out of line: only merges and failed merges come here, and inlined its registers would weigh on
+// every pod of the loop.
+__device__ __noinline__ void fl_rqc_spread(int32_t* col, int ncc, const int32_t* off, const int32_t* mem, int c, int32_t val) {
+  rqc_spread(col, ncc, off, mem, c, val);
+}
+// The full path's: the tables' addresses from LDS (set once per Solve), so that its three call sites keep no scalar
+// registers live for them; sl's class, and with `empty` the class without requirements as well (a creation).
+struct RqcTab {
+  int32_t* fail;
+  const int32_t *cls, *off, *mem;
+  int32_t ncc, empty;
+};
+__shared__ RqcTab g_rqc;
+__device__ __forceinline__ void fp_rqc_spread(int nc, int sl, int32_t val, bool empty) {
+  const RqcTab LDS* t = (const RqcTab LDS*)&g_rqc;
+  const int c = t->cls[sl];
+  rqc_spread(t->fail + nc, t->ncc, t->off, t->mem, c, val);
+  if (empty && t->empty >= 0 && t->empty != c) rqc_spread(t->fail + nc, t->ncc, t->off, t->mem, t->empty, val);
 }
 
 // kp_cancel: the caller's flag in host-mapped memory, read past every cache (system scope)
@@ -3017,7 +3056,9 @@ if (!FL_NOTIME && tmg) {                                    \
           }
           uint64_t X = 0, m_v = 0;
           ReqView rv;
-          bool perm = true;  // a failure here is permanent (NC_NEVER) unless it is Compatible's undefined-key rule
+          // a failure here is permanent (NC_NEVER) unless it is Compatible's undefined-key rule (0); 2: Compatible itself
+          // failed for good, which holds for the level's whole requirement class
+          int perm = 1;
           if (LIKELY(!full_add)) {
             if (LIKELY(n_rrp <= 4 && cat < 8)) {
               X = fits_lean(D, (const CatHdr LDS*)&g_hdr[cat], X0, q_lane, j0_lane, (const int64_t LDS*)g_fitv, rrp,
@@ -3041,7 +3082,7 @@ if (!FL_NOTIME && tmg) {                                    \
             const uint64_t b_negop = KA(shape_negop)[sl];
             bool mok = merge_compatible(D, crx, (const KReqs*)&fl_B, b_negop, true, m_v, rv,
                                         (WaveSlots*)&fl_slots, vig);
-            if (!mok) perm = (fl_B.present & ~crx.P & ~b_negop & ~D.wellknown) == 0;
+            if (!mok) perm = (fl_B.present & ~crx.P & ~b_negop & ~D.wellknown) == 0 ? 2 : 0;
             bytes += sizeof(KReqs);
             if (mok) {
               const int pb = KA(pvp_base)[sl * KA(n_catalogs) + cat];
@@ -3050,6 +3091,13 @@ if (!FL_NOTIME && tmg) {                                    \
                                q_lane, j0_lane, (const int64_t LDS*)g_fitv, KA(req_res_mask), vig, (uint32_t*)fl_scratch,
                                (RowPtr LDS*)fl_rl, &bytes, fl_fitj);
               bytes += (uint64_t)D.TW * 8 + KP_NRES * 8;
+            }
+          }
+          if (MERGE_DIAG && FT_FINE && tmg) {  // diagnostic: FTF(11)'s interval by the attempt's kind
+            const int kd = !full_add ? 4 : __ballot(X != 0) ? 0 : 2;
+            if (lane == 0) {
+              g_sdiag[kd] += 1;
+              g_sdiag[kd + 1] += __builtin_amdgcn_s_memtime() - ft;
             }
           }
           FTF(11);
@@ -3063,7 +3111,12 @@ if (!FL_NOTIME && tmg) {                                    \
             if (UNLIKELY(full_add)) {
               store_merged(reinterpret_cast<KReqs*>(KA(nc_reqs) + (size_t)ncx * sizeof(KReqs)), rv, m_v, D.W, D.KB);
               if (TOPO && KA(n_tk)) store_tcodes(KA(n_tk), KA(tk_keys), KA(nc_tcode), KA(hnc_stride), rv, m_v, ncx);
-              if (ncx < KA(ncc)) KA(nc_fail)[(size_t)sl * KA(ncc) + ncx] = NC_MERGED;  // (uniform: every lane)
+              if (ncx < KA(ncc)) {
+                KA(nc_fail)[(size_t)sl * KA(ncc) + ncx] = NC_MERGED;  // (uniform: every lane)
+                // the level's requirement class with it (a tagged level, here for minValues, brought it before)
+                if ((REQ_CLASSES & 1) && !TOPO && !tagged)
+                  fl_rqc_spread(KA(nc_fail) + ncx, KA(ncc), KA(rqc_off), KA(rqc_mem), KA(sl_rqc)[sl], NC_MERGED);
+              }
             }
             // the remaining types and threshold indices are stored only when they changed (the append path
             // usually leaves both as they were): fewer vector-memory operations ahead of the next pod's loads
@@ -3131,7 +3184,11 @@ if (!FL_NOTIME && tmg) {                                    \
             FTF(12);
             break;
           }
-          if (ncx < KA(ncc)) KA(nc_fail)[(size_t)sl * KA(ncc) + ncx] = perm ? NC_NEVER : verx;  // (every lane)
+          if (ncx < KA(ncc)) {
+            KA(nc_fail)[(size_t)sl * KA(ncc) + ncx] = perm ? NC_NEVER : verx;  // (every lane)
+            if ((REQ_CLASSES & 1) && !TOPO && UNLIKELY(perm == 2))
+              fl_rqc_spread(KA(nc_fail) + ncx, KA(ncc), KA(rqc_off), KA(rqc_mem), KA(sl_rqc)[sl], NC_NEVER);
+          }
         }
       }
       wave_sync();
@@ -3475,8 +3532,9 @@ __global__ __launch_bounds__(NW * 64) void solve_kernel(SolveArgs a0, const Solv
     g_fast.bytes = g_fast.attempts = g_fast.scanned = g_fast.starts = g_fast.fpods = g_fast.runpods = 0;
     for (int i = 0; i < 16; i++) g_fast.fcyc[i] = 0;
     for (int i = 0; i < 8; i++) g_fast.fbail[i] = 0;
-    if (SORT_DIAG || EX_DIAG || FX_DIAG)
+    if (SORT_DIAG || EX_DIAG || FX_DIAG || MERGE_DIAG)
       for (int i = 0; i < 6; i++) g_sdiag[i] = 0;
+    g_rqc = RqcTab{a.nc_fail, a.sl_rqc, a.rqc_off, a.rqc_mem, a.ncc, a.rqc_empty};
   }
   __syncthreads();
 
@@ -3961,7 +4019,8 @@ __global__ __launch_bounds__(NW * 64) void solve_kernel(SolveArgs a0, const Solv
         for (int r0 = 0, width = NW; r0 < n; r0 += width) {
           width = (s_list[r0] & LIST_TAG) ? 1 : NW;
           const int li = r0 + wave;
-          bool ok = false, fast = false, perm = true;
+          bool ok = false, fast = false;
+          int perm = 1;  // (as the fast lane's: 0 the undefined-key rule, 2 Compatible failed for good)
           uint64_t m_v = 0, X = 0, held = 0, nh = 0;
           ReqView rv;
           int nc = -1;
@@ -3986,7 +4045,7 @@ __global__ __launch_bounds__(NW * 64) void solve_kernel(SolveArgs a0, const Solv
               bytes += (uint64_t)D.TW * 8 + KP_NRES * 8 + 8;
             } else {
               ok = merge_compatible(D, cr, B, b_negop, true, m_v, rv, &slots[wave], vi);
-              if (!ok) perm = (B->present & ~cr.P & ~b_negop & ~D.wellknown) == 0;
+              if (!ok) perm = (B->present & ~cr.P & ~b_negop & ~D.wellknown) == 0 ? 2 : 0;
               bytes += sizeof(KReqs);
             }
             if (tsub && lane == 0) tsub[0] += __builtin_amdgcn_s_memtime() - tm0;
@@ -4008,6 +4067,8 @@ __global__ __launch_bounds__(NW * 64) void solve_kernel(SolveArgs a0, const Solv
               if (nh == ~0ull) ok = memo = false;
             }
             if (!ok && memo && lane == 0 && nc < a.ncc) a.nc_fail[(size_t)sl * a.ncc + nc] = perm ? NC_NEVER : a.nc_head[nc].ver;
+            if ((REQ_CLASSES & 2) && !TOPO && !ok && perm == 2 && nc < a.ncc)  // Compatible failed for good: the whole class
+              fp_rqc_spread(nc, sl, NC_NEVER, false);
           }
           if (lane == 0 && wave < width) s_ok[wave] = ok ? 1 : 0;
           __syncthreads();
@@ -4020,6 +4081,8 @@ __global__ __launch_bounds__(NW * 64) void solve_kernel(SolveArgs a0, const Solv
                 if (a.n_tk) store_tcodes(a.n_tk, a.tk_keys, a.nc_tcode, a.hnc_stride, rv, m_v, nc);
               }
               if (lane == 0 && nc < a.ncc) a.nc_fail[(size_t)sl * a.ncc + nc] = NC_MERGED;  // (count-independent)
+              if ((REQ_CLASSES & 2) && !TOPO && !fast && nc < a.ncc)  // a merge: the level's requirement class with it
+                fp_rqc_spread(nc, sl, NC_MERGED, false);
               if (lane < D.TW) a.nc_X[(size_t)nc * D.TW + lane] = X;
               if (lane < KP_NRES) a.nc_requests[(size_t)nc * KP_NRES + lane] += s_preq[lane];
               if (lane == 0 && hpa) a.nc_hp[nc] |= hpa;
@@ -4172,6 +4235,12 @@ __global__ __launch_bounds__(NW * 64) void solve_kernel(SolveArgs a0, const Solv
               }
               if (lane < KP_NRES) a.nc_fitj[(size_t)nc * KP_NRES + lane] = s_fitj[wave][lane];
               if (lane == 0 && nc < a.ncc) a.nc_fail[(size_t)sl * a.ncc + nc] = NC_MERGED;
+              if ((REQ_CLASSES & 2) && !TOPO && nc < a.ncc) {
+                // the creating level's requirement class, and the class without requirements: Add of such a pod is
+                // Fits alone on any NodeClaim (the full path's triv). Tagged on a NodeClaim with minValues as well: those
+                // take NodeClaim.Add in full whatever the tag says
+                fp_rqc_spread(nc, sl, NC_MERGED, true);
+              }
               if (a.res_mode) {
                 reserve_commit((int32_t LDS*)s_rcap, 0, nh);
                 if (lane == 0) a.nc_held[nc] = nh;
@@ -4364,7 +4433,7 @@ __global__ __launch_bounds__(NW * 64) void solve_kernel(SolveArgs a0, const Solv
     for (int i = 0; i < 6; i++) a.stats[25 + i] = g_fast.fcyc[i];
     if (FT_FINE && timing)
       for (int i = 0; i < 8; i++) a.stats[16 + i] = g_fast.fcyc[6 + i];
-    if (SORT_DIAG || EX_DIAG || FX_DIAG)
+    if (SORT_DIAG || EX_DIAG || FX_DIAG || MERGE_DIAG)
       for (int i = 0; i < 6; i++) a.stats[25 + i] = g_sdiag[i];
     // chunked order: peak chunks, splits, emptied chunks, (re)builds; final order mode
     a.stats[41] = g_chk.nch_peak;
@@ -4927,7 +4996,7 @@ __global__ __launch_bounds__(FEASB_WAVES * 64, FEASB_MINW) void feasibility_bits
 #define FEASQ_MINW 6  // waves per SIMD the quad kernel's register budget targets (8: 9 VGPRs spilled; 6: none, -4..6 %)
 #endif
 static_assert(KP_DIAG_BUILD || (FASTLANE == 1 && FL_NOTIME == 1 && FT_FINE == 0 && FAST_SCAN_MAX == 512 &&
-                                 FAST_CHK_LIVE == 8 && FAST_EX_ROUNDS == 8 && FAST_CONT == 1 && SORT_DIAG == 0 && EX_DIAG == 0 && FX_DIAG == 0 && FEAS_MAX_BLOCKS == 65536 &&
+                                 FAST_CHK_LIVE == 8 && FAST_EX_ROUNDS == 8 && FAST_CONT == 1 && SORT_DIAG == 0 && EX_DIAG == 0 && FX_DIAG == 0 && REQ_CLASSES == 3 && MERGE_DIAG == 0 && FEAS_MAX_BLOCKS == 65536 &&
                                  FEASQ_EW == 7 && FEASQ_ROWS == 28 && FEASQ_B128 == 1 && FEASQ_SKIP_EVAL == 0 && FL_SKIP == 0 &&
                                  FEASQ_MINW == 6),
               "the production build carries the production values of every measurement knob");

@@ -17,6 +17,11 @@
  *   SORT_DIAG [0]        the full path's sort split in stats[25..30]
  *   EX_DIAG [0]          the existing-node scan split in stats[25..30]
  *   FX_DIAG [0]          the fast lane's existing-node scans (scans, rounds, placed, skipped, failed, bailed) in stats[25..30]
+ *   REQ_CLASSES [3]      a merge / a permanent Compatible failure is memoised for the level's whole requirement class:
+ *                        bit 0 by the fast lane's writers, bit 1 by the full path's (0: for the level alone, as before
+ *                        requirement classes)
+ *   MERGE_DIAG [0]       with FT_FINE: the fast lane's attempt interval FTF(11) by kind in stats[25..30]: merges, failed
+ *                        full adds, appends (count, cycles each); KP_TIMING=1 MERGE_DIAG=1 tools/profile_solve.py
  *   FEAS_MAX_BLOCKS [65536], FEASQ_EW [7], FEASQ_ROWS [28], FEASQ_B128 [1]  feasibility grid / block shape
  *   FEASQ_SKIP_EVAL [0]  decode + copies only, no type-set work: WRONG MASKS, timing experiments only
  *   FEASQ_MINW [6]       feasibility_quad_kernel register budget (waves per SIMD)

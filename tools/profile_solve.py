@@ -44,6 +44,13 @@ if os.environ.get("EX_DIAG"):  # variant build: the existing-node scan in place 
                                     zip(["staging_cycles", "prepass_cycles", "attempt_cycles", "scans", "cycles", "eval_cycles"], fc)}
 if os.environ.get("FX_DIAG"):  # variant build: the fast lane's existing-node scans (counts over the Solve)
     out["fast_existing_scans"] = dict(zip(["scans", "rounds", "placed", "skipped", "failed", "bailed"], fc))
+if os.environ.get("MERGE_DIAG"):  # variant build (FT_FINE + MERGE_DIAG): the fast lane's attempt interval FTF(11) by kind
+    tot_k = float(sum(st["phase_cycles"])) or 1.0
+    out["merge_diag"] = {k: {"count": fc[2 * i], "cycles": fc[2 * i + 1],
+                             "cycles_each": round(fc[2 * i + 1] / max(1, fc[2 * i]), 1),
+                             "share_of_phase_cycles": round(fc[2 * i + 1] / tot_k, 4)}
+                         for i, k in enumerate(["merges", "failed_full_adds", "appends"])}
+    out["phase_cycles_total"] = tot_k
 if os.environ.get("SORT_DIAG"):  # variant build: the full path's sort split in place of the fast-lane phases
     out["sort_diag_per_pop"] = {k: round(v / max(1, st["pops"]), 2) for k, v in
                                 zip(["decision_cycles", "shift_cycles", "shifted", "mode1", "mode2", "mode3"], fc)}
