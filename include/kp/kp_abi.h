@@ -26,6 +26,8 @@
  *                             apply the NodePools' disruption budgets (disruption.md:274-333) per subset on the device.
  *   kp_cluster_command     <- the Command computeConsolidation returns: the replacement NodeClaim (options after the
  *                             price filters, requirements, requests, pods) and where every rescheduled pod went.
+ *   kp_cluster_validate    <- upstream Validation.ValidateCommand: the command re-simulated on a plan of current state
+ *                             and accepted only if the new simulation agrees with it.
  *
  * Conventions
  *   - Every function returns int32: KP_OK (0) or a negative KP_E_* code. kp_last_error() gives text.
@@ -977,6 +979,69 @@ int32_t kp_cluster_drift(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_
 int32_t kp_cluster_command(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
                            uint32_t n_subsets, int32_t multi_node, const uint32_t* allowed, uint32_t n_allowed,
                            kp_sim_result* out, kp_solve_result** commands, uint64_t* n_blocked, kp_solve_stats* stats);
+/* Command validation (upstream disruption/validation.go, v1.5.1: Validation.IsValid / ValidateCommand, the step
+ * SingleNodeConsolidation and MultiNodeConsolidation run between computing a command and executing it), additive to ABI
+ * v13. The upstream file is not among this project's references: the rule below is RESTATED here, only the 15 s
+ * consolidation TTL is documented (R:website/content/en/v0.32/upgrading/v1beta1-migration.md:404), and parity beyond
+ * the rule is unpinned. The plan is one prepared from CURRENT state; subset s holds the command's candidates and
+ * checks[s] what the command decided. Let r be SimulateScheduling of the candidates on the plan - the simulation
+ * kp_cluster_simulate builds (pending pods, the deleting nodes' pods and the candidates' pods queued; every other
+ * non-deleting node existing; strict reservations; Truncate(100) with its minValues check; the NodePools' remaining
+ * limits). In this order:
+ *   1. some non-pending pod of r is unscheduled, or a candidate pod sits on an uninitialized node (a NodeClaim whose
+ *      truncated options break minValues has lost its pods):                          KP_INVALID_UNSCHEDULED
+ *   2. r makes no NodeClaim: a command without replacement is KP_VALID, one with a replacement
+ *      KP_INVALID_NO_REPLACEMENT_NEEDED (upstream: "scheduling simulation produced new results")
+ *   3. r makes more than one NodeClaim:                                                KP_INVALID_MULTIPLE
+ *   4. r makes one NodeClaim and the command has no replacement:                       KP_INVALID_NEEDS_REPLACEMENT
+ *   5. r makes one NodeClaim and the command has one: the command's options must be a subset, as a set of
+ *      instance-type names, of the new NodeClaim's options - its whole price-ordered list after Truncate, NOT the ones
+ *      a price filter would keep: KP_VALID, else KP_INVALID_NOT_SUBSET with n_missing the names that are absent.
+ * Validation applies no price filter, no same-type filter and no spot-to-spot rule, so there is no multi_node input.
+ * r stops at its second NodeClaim, as every consolidation simulation here does: the pods it had not reached are in no
+ * state yet, so a simulation that needs more than one NodeClaim reports rule 3 (n_nodeclaims 2, n_unscheduled 0)
+ * whether or not rule 1 would also have held of the finished Solve; both are invalid.
+ * Names are a set (duplicates count once); a name the new NodeClaim's catalogue does not hold counts as missing.
+ * A subset the budget rule of kp_cluster_simulate_budgeted blocks (the caller asks with the command's reason) is not
+ * simulated: KP_INVALID_BUDGET, blocked = 1, every count 0; it counts in *n_blocked. allowed == NULL: no budgets.
+ * Errors: KP_E_INVAL for a decision other than KP_DECISION_DELETE / KP_DECISION_REPLACE, a REPLACE without options and
+ * a NULL name; otherwise those of kp_cluster_simulate_budgeted (a deleting node in a subset, the pool label,
+ * n_allowed), with its stale-plan refusal (kp_catalog_update_offerings until kp_cluster_refresh), cancellation (the
+ * plan stays usable) and stats words. On a plan of the batched simulation kernel the checking sim_kernel instantiation
+ * writes the records; on a general-path plan validate_verdict_kernel writes them behind the batched launches'
+ * solve_kernel and finalize_kernel (Truncate's minValues check on the device), and a subset compiled on its own takes
+ * the rule on the host from that Solve's result (every subset does when the cluster has both capacity reservations and
+ * minValues: the held reservation ids join the requirements before the minValues check, which only the host does).
+ * NodePool limits on a batched-kernel plan: the kernel judges a second NodeClaim by the limits the pass began with,
+ * while the first NodeClaim has taken its largest option out of them (subtractMax), so a subset it reports as MULTIPLE
+ * is run once more as its own whole Solve and the record is that Solve's (UNSCHEDULED with one NodeClaim where the
+ * limits admit no second); the caller pays one compile and Solve per such subset. stats: as kp_cluster_simulate reports
+ * them on either kind of plan. */
+enum kp_validity {
+  KP_VALID = 0,
+  KP_INVALID_UNSCHEDULED = 1,
+  KP_INVALID_NO_REPLACEMENT_NEEDED = 2,
+  KP_INVALID_MULTIPLE = 3,
+  KP_INVALID_NEEDS_REPLACEMENT = 4,
+  KP_INVALID_NOT_SUBSET = 5,
+  KP_INVALID_BUDGET = 6
+};
+typedef struct kp_command_check {
+  int32_t decision;             /* KP_DECISION_DELETE (no replacement) or KP_DECISION_REPLACE */
+  const char* const* options;   /* REPLACE: the command's InstanceTypeOptions, by instance-type name */
+  uint32_t n_options;
+} kp_command_check;
+typedef struct kp_validation {
+  int32_t  verdict;         /* enum kp_validity */
+  uint32_t n_nodeclaims;    /* 0, 1, or 2 = more than one */
+  uint32_t n_pods;          /* pods queued */
+  uint32_t n_unscheduled;   /* rule 1: non-pending pods unscheduled or on an uninitialized node */
+  uint32_t n_missing;       /* NOT_SUBSET: command options absent from the new NodeClaim's options */
+  uint32_t blocked;         /* 1: not simulated (budget) */
+} kp_validation;
+int32_t kp_cluster_validate(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
+                            uint32_t n_subsets, const kp_command_check* checks, const uint32_t* allowed,
+                            uint32_t n_allowed, kp_validation* out, uint64_t* n_blocked, kp_solve_stats* stats);
 /* The reduction kp_consolidate_argmin applies to the gathered per-rank records (host-only; exposed for callers that
  * reduce over another transport, and for tests): counts are summed, the best record wins. */
 int32_t kp_choice_reduce(const kp_choice* per_rank, uint32_t n, kp_choice* out);

@@ -436,11 +436,13 @@ struct SimArgs {
 struct SimAll {
   static constexpr bool gated = false;
   static constexpr bool emit = false;
+  static constexpr bool check = false;
   static constexpr const uint32_t* live = nullptr;
 };
 struct SimLive {
   static constexpr bool gated = true;
   static constexpr bool emit = false;
+  static constexpr bool check = false;
   const uint32_t* live;
 };
 // The emitting instantiation (kp_cluster_command): gated as SimLive, and every simulation also leaves the command it
@@ -464,9 +466,30 @@ struct SimCmdHdr {
 struct SimEmit {
   static constexpr bool gated = true;
   static constexpr bool emit = true;
+  static constexpr bool check = false;
   const uint32_t* live;
   uint8_t* rec;
   size_t stride;  // sim_cmd_stride(cap)
+};
+// The checking instantiation (kp_cluster_validate): gated as SimEmit (the identity list without budgets). A simulation
+// takes no consolidation decision: it runs to its end (a candidate pod on an uninitialized node is counted, not a
+// stop), and one that made exactly one NodeClaim tests the caller's options - want, one type bitmask of TW words per
+// (subset, catalogue), names resolved on the host; unknown the count of names that catalogue does not hold - against
+// the NodeClaim's whole truncated option list. It leaves one ValOut (kp_validation) at the caller's subset index: six
+// words, lane w writes word w, plain vector stores.
+struct ValOut {
+  int32_t verdict;
+  uint32_t n_nodeclaims, n_pods, n_unscheduled, n_missing, blocked;
+};
+struct SimCheck {
+  static constexpr bool gated = true;
+  static constexpr bool emit = false;
+  static constexpr bool check = true;
+  const uint32_t* live;
+  const uint64_t* want;     // [n_subsets][n_catalogs][TW]
+  const uint32_t* unknown;  // [n_subsets][n_catalogs]
+  const uint8_t* replace;   // [n_subsets] 1: the command carries a replacement
+  uint32_t* val;            // [n_subsets] ValOut
 };
 inline size_t sim_cmd_stride(int cap) { return (sizeof(SimCmdHdr) + (size_t)12 * cap + 15) & ~(size_t)15; }
 // budget gate over the resident CSR batch (budget_gate_kernel, gate_scan_kernel, gate_scatter_kernel)
@@ -527,6 +550,22 @@ struct DriftArgs {
   DriftOut* out;                 // [n_subsets] caller order
   DriftRec* rec;                 // [1] this launch's record
 };
+// kp_cluster_validate on general-path plans: validate_verdict_kernel and validate_sum_kernel behind a launch's
+// solve_kernel and finalize_kernel (d.out unused; d.rec: the launch's counters)
+struct ValidateArgs {
+  DriftArgs d;
+  size_t off_nct, off_nopt, off_opts, off_ncr;  // NodeClaim 0 within an arena: template, option count, options, final KReqs
+  int32_t opt_stride;            // options an arena holds per NodeClaim
+  int32_t n_tmpl, n_catalogs;
+  const DevDict* dict;
+  const DevCatalog* cats;
+  const int32_t* tmpl_catalog;   // [n_tmpl]
+  const uint64_t* want;          // [n_subsets][n_catalogs][TW], caller order (as SimCheck)
+  const uint32_t* unknown;       // [n_subsets][n_catalogs]
+  const uint8_t* replace;        // [n_subsets]
+  ValOut* out;                   // [n_subsets] caller order
+};
+hipError_t launch_validate_verdict(const ValidateArgs& a, hipStream_t s);
 hipError_t launch_drift_verdict(const DriftArgs& a, hipStream_t s);
 hipError_t launch_drift_first(const DriftArgs& a, hipStream_t s);
 // finalize over every NodeClaim of the launch's first feasible simulation (rec->local), `max_nc` workgroups
@@ -554,6 +593,9 @@ const void* sim_kernel_ptr(bool gated = false);
 // the emitting instantiation (kp_cluster_command): as launch_sim_gated, with the command records
 hipError_t launch_sim_emit(const SimArgs& a, const SimEmit& em, int n_live, int blocks, size_t dyn_lds, hipStream_t s);
 const void* sim_emit_kernel_ptr();
+// the checking instantiation (kp_cluster_validate): as launch_sim_gated, with the checks and the verdict records
+hipError_t launch_sim_check(const SimArgs& a, const SimCheck& ck, int n_live, int blocks, size_t dyn_lds, hipStream_t s);
+const void* sim_check_kernel_ptr();
 #define SIM_WAVES 4
 
 hipError_t launch_solve(const SolveArgs& a, int nw, size_t dyn_lds, hipStream_t s);

@@ -6171,6 +6171,19 @@ struct DriftRun {
 };
 static int32_t DriftSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand, int s, DriftRun& dr, uint64_t* counters,
                            double* dev_ms, kp_cancel* cancel);
+// kp_cluster_validate's state across the launches of one call (GeneralBatchRun in validation mode, ValidateSimOne)
+struct ValRun {
+  const kp_command_check* checks = nullptr;
+  vector<vector<string>> names;  // per subset: the check's names as a set
+  vector<ValOut> host_out;       // caller order: the verdicts taken on the host (subsets compiled on their own) ...
+  vector<char> on_host;          // ... and which entries those are; the rest come from the device array
+  ValOut* d_out = nullptr;       // [n_subsets] validate_verdict_kernel's records, caller order
+  const uint64_t* d_want = nullptr;
+  const uint32_t* d_unknown = nullptr;
+  const uint8_t* d_replace = nullptr;
+};
+static int32_t ValidateSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand, int s, ValRun& vl, uint64_t* counters,
+                              double* dev_ms, kp_cancel* cancel);
 static int32_t DriftFetch(kp_cluster_plan* plan, GeneralBatch& gb, const GenSlot& sl, int j, const vector<uint32_t>& cand,
                           std::unique_ptr<kp_solve_result>& out);
 
@@ -6181,7 +6194,7 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
                                const vector<int>& idx, const vector<std::map<string, string>>& labels, int32_t multi_node,
                                vector<SimOut>& outs, uint64_t* counters, double* dev_ms, double* host_ms,
                                kp_cancel* cancel, uint64_t* n_launches, DriftRun* dr = nullptr,
-                               kp_solve_result** commands = nullptr) {
+                               kp_solve_result** commands = nullptr, ValRun* vl = nullptr) {
   kp_ctx* ctx = plan->ctx;
   const kp_cluster& cl = plan->cluster()->cl;
   const Compiled& C = *gb.C;
@@ -6254,7 +6267,10 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
   const size_t d_qlen = sizeof(int32_t) * (size_t)Pc * per_launch, d_cidx = d_qlen + sizeof(int32_t) * per_launch;
   const size_t d_rec = (d_cidx + sizeof(int32_t) * per_launch + 255) & ~(size_t)255;
   const size_t u_drift = (u_end + 255) & ~(size_t)255;
-  const size_t up_need = dr ? u_drift + d_rec : u_end, down_need = dr ? sizeof(DriftRec) : r_end;
+  // (validation launches, vl: the same buffers; their Solves stop at the second NodeClaim and are finalized as the
+  // consolidation launches are, then validate_verdict_kernel and validate_sum_kernel leave the verdicts and one record)
+  const bool rec_mode = dr || vl;
+  const size_t up_need = rec_mode ? u_drift + d_rec : u_end, down_need = rec_mode ? sizeof(DriftRec) : r_end;
 
   // the host decisions of a finished launch (its results in the slot's download buffer)
   auto decide = [&](GenSlot& sl) -> int32_t {
@@ -6377,7 +6393,22 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
     host_ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th1).count();
     return KP_OK;
   };
-  auto decide_any = [&](GenSlot& sl) -> int32_t { return dr ? decide_drift(sl) : decide(sl); };
+  // validation: the launch's record (counters, a runaway Solve, cancellation)
+  auto decide_val = [&](GenSlot& sl) -> int32_t {
+    HIPCHK(hipEventSynchronize(sl.done));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, sl.t0, sl.t1));
+    *dev_ms += ms;
+    const DriftRec rec = *reinterpret_cast<const DriftRec*>(sl.down.at(0));
+    counters[0] += rec.attempts;
+    counters[1] += rec.bytes;
+    counters[2] += rec.pops;
+    if (rec.runaway >= 0)
+      return fail(KP_E_DEVICE, "solve_kernel exceeded its Queue.Pop bound in simulation %lld: aborted", (long long)rec.runaway);
+    if (rec.cancelled) return fail(KP_E_CANCELED, "validation simulations cancelled (kp_cancel_set)");
+    return KP_OK;
+  };
+  auto decide_any = [&](GenSlot& sl) -> int32_t { return vl ? decide_val(sl) : dr ? decide_drift(sl) : decide(sl); };
 
   GenSlot* slots = gb.slot;
   for (int k = 0; k < 2; k++)
@@ -6423,7 +6454,7 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
     }
     if (ae == hipSuccess) ae = sl.up.reserve(up_need);
     if (ae == hipSuccess) ae = sl.down.reserve(down_need);
-    if (ae == hipSuccess && dr && sl.drift_bytes < d_rec + sizeof(DriftRec)) {
+    if (ae == hipSuccess && rec_mode && sl.drift_bytes < d_rec + sizeof(DriftRec)) {
       ae = sl.drift.alloc(d_rec + sizeof(DriftRec));
       sl.drift_bytes = ae == hipSuccess ? d_rec + sizeof(DriftRec) : 0;
     }
@@ -6434,7 +6465,8 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
         pending = -1;
       }
       for (size_t j = b0; j < idx.size(); j++)
-        if (int32_t rc = dr ? DriftSimOne(plan, cands[order[j]], order[j], *dr, counters, dev_ms, cancel)
+        if (int32_t rc = vl ? ValidateSimOne(plan, cands[order[j]], order[j], *vl, counters, dev_ms, cancel)
+                         : dr ? DriftSimOne(plan, cands[order[j]], order[j], *dr, counters, dev_ms, cancel)
                             : GeneralSimOne(plan, cands[order[j]], labels, multi_node, outs[order[j]], counters, dev_ms, cancel,
                                             commands ? &commands[order[j]] : nullptr))
           return rc;
@@ -6538,7 +6570,7 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
     HIPCHK(hipMemcpyAsync(dfargs, reinterpret_cast<uint8_t*>(sl.up.at(u_fargs)), sizeof(FinalizeArgs) * n, hipMemcpyHostToDevice, up));
     DriftArgs da;
     memset(&da, 0, sizeof da);
-    if (dr) {
+    if (rec_mode) {
       uint8_t* hd = sl.up.at(u_drift);
       uint8_t* dd = (uint8_t*)sl.drift.p;
       int32_t* qpod = reinterpret_cast<int32_t*>(hd);
@@ -6566,7 +6598,7 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
       da.pod_kind = gb.d_pod_kind;
       da.pod_cluster = gb.d_pod_cluster;
       da.pos_uninit = gb.d_pos_uninit;
-      da.out = dr->d_out;
+      da.out = dr ? dr->d_out : nullptr;
       da.rec = reinterpret_cast<DriftRec*>(dd + d_rec);
     }
     HIPCHK(hipEventRecord(sl.uploaded, up));
@@ -6584,10 +6616,27 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
     } else {
       HIPCHK(launch_finalize_batch(fargs[0], dfargs, n, ks));
     }
+    if (vl) {
+      ValidateArgs va;
+      memset(&va, 0, sizeof va);
+      va.d = da;
+      va.off_nct = o.nct, va.off_nopt = o.nopt, va.off_opts = o.opts, va.off_ncr = o.ncr;
+      va.opt_stride = gb.opt_stride;
+      va.n_tmpl = (int32_t)C.B->tmpl_catalog.size();
+      va.n_catalogs = (int32_t)C.B->cats.size();
+      va.dict = sargs[0].dict;
+      va.cats = sargs[0].cats;
+      va.tmpl_catalog = sargs[0].tmpl_catalog;
+      va.want = vl->d_want;
+      va.unknown = vl->d_unknown;
+      va.replace = vl->d_replace;
+      va.out = vl->d_out;
+      HIPCHK(launch_validate_verdict(va, ks));
+    }
     HIPCHK(hipEventRecord(sl.t1, ks));
     // downloads on their own stream once the kernels are done (the next launch's kernels need not wait for them)
     HIPCHK(hipStreamWaitEvent(dn, sl.t1, 0));
-    if (dr) {  // drift launches download the record only (the verdicts: one copy at the end of the call)
+    if (rec_mode) {  // drift and validation launches download the record only (the verdicts: one copy at the end of the call)
       HIPCHK(hipMemcpyAsync(sl.down.at(0), da.rec, sizeof(DriftRec), hipMemcpyDeviceToHost, dn));
     } else {
       auto down = [&](size_t roff, size_t off, size_t width) {
@@ -7001,9 +7050,18 @@ struct CmdEmit {
   int cap = 0;
   kp_solve_result** commands = nullptr;  // general-path plans: filled from the batched launches' arenas
 };
+// kp_cluster_validate on a plan of the batched kernel: the checks compiled for the device (ValidateCompile), and where
+// the launch leaves the verdict records and, with budgets, the gate's bytes
+struct ValCheck {
+  vector<uint64_t> want;     // [n_subsets][n_catalogs][TW] type bitmask of the command's options
+  vector<uint32_t> unknown;  // [n_subsets][n_catalogs] its names the catalogue does not hold
+  vector<uint8_t> replace;   // [n_subsets] 1: the command carries a replacement
+  const uint8_t* val = nullptr;   // device: [n_subsets] ValOut
+  const uint8_t* gate = nullptr;  // device: [n_subsets] 1 admissible, 0 blocked (budgets only)
+};
 static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, const uint32_t* nodes, uint32_t n_subsets,
                                int32_t multi_node, SimArgs& a_out, kp_cancel* cancel, BudgetGate* bg = nullptr,
-                               CmdEmit* em = nullptr) {
+                               CmdEmit* em = nullptr, ValCheck* vc = nullptr) {
   kp_ctx* ctx = plan->ctx;
   if (cancel && __atomic_load_n(cancel->flag, __ATOMIC_SEQ_CST))
     return fail(KP_E_CANCELED, "cancelled before the simulations");
@@ -7049,7 +7107,7 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
     a.cancel = (const int32_t*)dp;
   }
   hipFuncAttributes fa;
-  HIPCHK(hipFuncGetAttributes(&fa, em ? sim_emit_kernel_ptr() : sim_kernel_ptr(bg != nullptr)));
+  HIPCHK(hipFuncGetAttributes(&fa, vc ? sim_check_kernel_ptr() : em ? sim_emit_kernel_ptr() : sim_kernel_ptr(bg != nullptr)));
   const size_t lds_wg = fa.sharedSizeBytes + (size_t)SIM_WAVES * a.wave_lds;
   if (lds_wg > 160 * 1024) return fail(KP_E_UNSUPPORTED, "simulation LDS %zu B per workgroup (cluster or subsets too large)", lds_wg);
   const int wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds_wg));
@@ -7097,7 +7155,7 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
   const size_t b_out = al(sizeof(SimOut) * n_subsets);
   // the budget gate's regions: gate bytes, live list, block counts and offsets, allowed[], the live count
   const uint32_t n_gblk = (n_subsets + GATE_BLOCK - 1) / GATE_BLOCK;
-  const size_t g_gate = bg ? al(n_subsets) : 0, g_live = bg || em ? al(sizeof(uint32_t) * n_subsets) : 0;
+  const size_t g_gate = bg ? al(n_subsets) : 0, g_live = bg || em || vc ? al(sizeof(uint32_t) * n_subsets) : 0;
   const size_t g_blk = bg ? al(sizeof(uint32_t) * n_gblk) : 0, g_allowed = bg ? al(sizeof(uint32_t) * (plan->n_pools + 1)) : 0;
   // the command records (kp_cluster_command), sized from the batch: behind everything else
   const size_t o_rec = b_off + b_nodes + b_out + g_gate + g_live + 2 * g_blk + g_allowed + (bg ? 256 : 0);
@@ -7107,7 +7165,11 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
   if (em && rec_stride * (size_t)n_subsets > ((size_t)4 << 30))
     return fail(KP_E_UNSUPPORTED, "%u subsets of up to %d pods: %zu B of command records (max 4 GiB per call)", n_subsets, cap,
                 rec_stride * (size_t)n_subsets);
-  const size_t b_total = o_rec + al(rec_stride * n_subsets);
+  // the checks and the verdict records (kp_cluster_validate): behind those
+  const size_t o_chk = o_rec + al(rec_stride * n_subsets);
+  const size_t v_want = vc ? al(sizeof(uint64_t) * vc->want.size()) : 0, v_unk = vc ? al(sizeof(uint32_t) * vc->unknown.size()) : 0;
+  const size_t v_rep = vc ? al(n_subsets) : 0, v_val = vc ? al(sizeof(ValOut) * n_subsets) : 0;
+  const size_t b_total = o_chk + v_want + v_unk + v_rep + v_val;
   if (b_total > plan->batch_bytes) {
     if (plan->batch.p) HIPCHK(hipFree(plan->batch.p));
     plan->batch.p = nullptr;
@@ -7125,6 +7187,15 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
   HIPCHK(hipMemsetAsync(a.s_ncfail, 0xFF, sz_fail, st));
   HIPCHK(hipMemsetAsync(a.stats, 0, sizeof(uint64_t) * 8, st));
   SimEmit se{nullptr, bb + o_rec, rec_stride};
+  SimCheck sc{nullptr, (const uint64_t*)(bb + o_chk), (const uint32_t*)(bb + o_chk + v_want), bb + o_chk + v_want + v_unk,
+              (uint32_t*)(bb + o_chk + v_want + v_unk + v_rep)};
+  if (vc) {
+    HIPCHK(hipMemcpyAsync((void*)sc.want, vc->want.data(), sizeof(uint64_t) * vc->want.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync((void*)sc.unknown, vc->unknown.data(), sizeof(uint32_t) * vc->unknown.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync((void*)sc.replace, vc->replace.data(), n_subsets, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(sc.val, 0, sizeof(ValOut) * n_subsets, st));
+    vc->val = (const uint8_t*)sc.val;
+  }
   if (em) {
     em->rec = bb + o_rec;
     em->stride = rec_stride;
@@ -7161,23 +7232,26 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
     plan->sim_waves[0] = n_live ? (uint64_t)a.n_slots : 0;  // (no live subset: nothing is launched)
     plan->sim_waves[1] = (n_live + (uint32_t)a.n_slots - 1) / (uint32_t)a.n_slots;
     HIPCHK(hipEventRecord(ctx->ev0, st));
-    se.live = g.live;
-    if (n_live && em) HIPCHK(launch_sim_emit(a, se, (int)n_live, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
+    se.live = sc.live = g.live;
+    if (vc) vc->gate = g.gate;
+    if (n_live && vc) HIPCHK(launch_sim_check(a, sc, (int)n_live, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
+    else if (n_live && em) HIPCHK(launch_sim_emit(a, se, (int)n_live, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
     else if (n_live) HIPCHK(launch_sim_gated(a, g.live, (int)n_live, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
     HIPCHK(hipEventRecord(ctx->ev1, st));
     return KP_OK;
   }
-  if (em) {
-    // No budgets: the emitting instantiation walks every subset, in order, through an identity list. An ungated
+  if (em || vc) {
+    // No budgets: the emitting (and the checking) instantiation walks every subset, in order, through an identity list. An ungated
     // emitting policy would be a fourth sim_kernel instantiation (its own code object and resource figures to hold)
     // to save one 4 * n_subsets byte upload on a call made for a few subsets.
     uint32_t* live = (uint32_t*)(bb + b_off + b_nodes + b_out);
     plan->cmd_live.resize(n_subsets);
     for (uint32_t s = 0; s < n_subsets; s++) plan->cmd_live[s] = s;
     HIPCHK(hipMemcpyAsync(live, plan->cmd_live.data(), sizeof(uint32_t) * n_subsets, hipMemcpyHostToDevice, st));
-    se.live = live;
+    se.live = sc.live = live;
     HIPCHK(hipEventRecord(ctx->ev0, st));
-    HIPCHK(launch_sim_emit(a, se, (int)n_subsets, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
+    if (vc) HIPCHK(launch_sim_check(a, sc, (int)n_subsets, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
+    else HIPCHK(launch_sim_emit(a, se, (int)n_subsets, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
     HIPCHK(hipEventRecord(ctx->ev1, st));
     return KP_OK;
   }
@@ -7416,6 +7490,268 @@ int32_t kp_cluster_command(kp_cluster_plan* plan, kp_cancel* cancel, const uint3
     return rc;
   }
   if (n_blocked && allowed) *n_blocked = bg.blocked;
+  return KP_OK;
+}
+
+// ---- Command validation (kp_cluster_validate) --------------------------------------------------------------------
+static_assert(sizeof(ValOut) == sizeof(kp_validation), "ValOut mirrors kp_validation");
+
+// A check's names as a set, in first-mention order; KP_E_INVAL as kp_abi.h lists it.
+static int32_t CheckNames(const kp_command_check& c, uint32_t s, vector<string>& names) {
+  names.clear();
+  if (c.decision != KP_DECISION_DELETE && c.decision != KP_DECISION_REPLACE)
+    return fail(KP_E_INVAL, "check %u: decision %d (KP_DECISION_DELETE or KP_DECISION_REPLACE)", s, c.decision);
+  if (c.decision == KP_DECISION_DELETE) return KP_OK;
+  if (!c.n_options || !c.options) return fail(KP_E_INVAL, "check %u: a replacement without options", s);
+  std::set<string> seen;
+  for (uint32_t j = 0; j < c.n_options; j++) {
+    if (!c.options[j]) return fail(KP_E_INVAL, "check %u: option %u is a null name", s, j);
+    if (seen.insert(c.options[j]).second) names.push_back(c.options[j]);
+  }
+  return KP_OK;
+}
+
+// The checks for the device: per (subset, catalogue) the options' type bitmask, names resolved through that
+// catalogue's name table, and the count of names it does not hold.
+static int32_t ValidateCompile(const vector<const kp_catalog*>& cats, int TW, const kp_command_check* checks,
+                               uint32_t n_subsets, ValCheck& vc) {
+  const size_t NC = cats.size();
+  vector<std::unordered_map<string, int>> table(NC);
+  vc.want.assign((size_t)n_subsets * NC * TW, 0);
+  vc.unknown.assign((size_t)n_subsets * NC, 0);
+  vc.replace.assign(n_subsets, 0);
+  vector<string> names;
+  for (uint32_t s = 0; s < n_subsets; s++) {
+    if (int32_t rc = CheckNames(checks[s], s, names)) return rc;
+    if (checks[s].decision != KP_DECISION_REPLACE) continue;
+    vc.replace[s] = 1;
+    for (size_t c = 0; c < NC; c++) {
+      if (table[c].empty())
+        for (size_t t = 0; t < cats[c]->types.size(); t++) table[c].emplace(cats[c]->types[t].name, (int)t);
+      uint64_t* row = &vc.want[((size_t)s * NC + c) * TW];
+      for (const string& nm : names) {
+        auto it = table[c].find(nm);
+        if (it == table[c].end() || it->second >= TW * 64) vc.unknown[(size_t)s * NC + c]++;
+        else row[it->second >> 6] |= 1ull << (it->second & 63);
+      }
+    }
+  }
+  return KP_OK;
+}
+
+// A subset compiled on its own (GeneralSolveOne: SimulateScheduling's Problem compiled from the subset, run as a whole
+// Solve): the rule applied to that Solve's result on the host. kp_solve_run has applied the held reservations and
+// Truncate's minValues check to the NodeClaim (HostMinValuesOK: options cleared, pods unplaced).
+static int32_t ValidateSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand, int s, ValRun& vl, uint64_t* counters,
+                              double* dev_ms, kp_cancel* cancel) {
+  SimOneSolve so;
+  if (int32_t rc = GeneralSolveOne(plan, cand, so, counters, dev_ms, cancel)) return rc;
+  const kp_cluster& cl = plan->cluster()->cl;
+  const kp_solve_result* res = so.res.get();
+  const bool repl = vl.checks[s].decision == KP_DECISION_REPLACE;
+  ValOut& v = vl.host_out[s];
+  memset(&v, 0, sizeof v);
+  vl.on_host[s] = 1;
+  v.n_pods = (uint32_t)so.kind.size();
+  if (res->ncs.size() > 1) {
+    v.verdict = KP_INVALID_MULTIPLE;
+    v.n_nodeclaims = 2;
+    return KP_OK;
+  }
+  v.n_nodeclaims = (uint32_t)res->ncs.size();
+  for (size_t p = 0; p < so.kind.size(); p++) {
+    const int32_t pl = res->placement[p];
+    if (so.kind[p] == 2) continue;
+    if (pl == -1 || (so.kind[p] == 0 && pl <= -2 && !so.ex[(size_t)(-2 - pl)].initialized)) v.n_unscheduled++;
+  }
+  if (v.n_unscheduled) {
+    v.verdict = KP_INVALID_UNSCHEDULED;
+  } else if (res->ncs.empty()) {
+    v.verdict = repl ? KP_INVALID_NO_REPLACEMENT_NEEDED : KP_VALID;
+  } else if (!repl) {
+    v.verdict = KP_INVALID_NEEDS_REPLACEMENT;
+  } else {
+    const vector<HostType>& types = cl.catalogs[res->nc_cat[0]]->types;
+    std::set<string> have;
+    for (uint32_t t : res->ncs[0].options)
+      if (t < types.size()) have.insert(types[t].name);
+    for (const string& nm : vl.names[s])
+      if (!have.count(nm)) v.n_missing++;
+    v.verdict = v.n_missing ? KP_INVALID_NOT_SUBSET : KP_VALID;
+  }
+  return KP_OK;
+}
+
+// General-path plans. Batched subsets: solve_kernel (stop at the second NodeClaim), finalize_kernel,
+// validate_verdict_kernel and validate_sum_kernel per launch (GeneralBatchRun); a launch downloads its record, the
+// verdicts come back in one copy at the end. Subsets compiled on their own: ValidateSimOne.
+static int32_t ValidateGeneralLocked(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
+                                     uint32_t n_subsets, const kp_command_check* checks, BudgetGate* bg, kp_validation* out,
+                                     uint64_t* counters, double* dev_ms, uint64_t* kst) {
+  kp_ctx* ctx = plan->ctx;
+  if (cancel && __atomic_load_n(cancel->flag, __ATOMIC_SEQ_CST))
+    return fail(KP_E_CANCELED, "cancelled before the simulations");
+  ValRun vl;
+  vl.checks = checks;
+  vl.names.resize(n_subsets);
+  for (uint32_t s = 0; s < n_subsets; s++)
+    if (int32_t rc = CheckNames(checks[s], s, vl.names[s])) return rc;
+  vector<vector<uint32_t>> cands;
+  vector<int> batched, single;
+  vector<char> blocked;
+  if (int32_t rc = GeneralPartition(plan, offsets, nodes, n_subsets, bg, false, cands, batched, single, &blocked)) return rc;
+  // held reservation ids are merged into a NodeClaim's requirements before Truncate's minValues check (ApplyHeld);
+  // validate_verdict_kernel checks the finalized requirements as they are, so a superset compile with both
+  // reservations and minValues takes the host's verdict for every subset
+  if (plan->gb && plan->gb->res_mode && plan->gb->min_values) {
+    single.insert(single.end(), batched.begin(), batched.end());
+    std::sort(single.begin(), single.end());
+    batched.clear();
+  }
+  vl.host_out.assign(n_subsets, ValOut{});
+  vl.on_host.assign(n_subsets, 0);
+  uint64_t n_launches = 0;
+  double host_ms[2] = {0, 0};
+  DevBuf dev;  // the compiled checks and the verdict records of this call
+  if (!batched.empty()) {
+    GeneralBatch& gb = *plan->gb;
+    if (int32_t rc = DriftTables(ctx, gb, plan->cluster()->cl)) return rc;
+    ValCheck vc;
+    if (int32_t rc = ValidateCompile(gb.C->B->catalogs, gb.C->B->TW, checks, n_subsets, vc)) return rc;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_unk = al(sizeof(uint64_t) * vc.want.size()), o_rep = o_unk + al(sizeof(uint32_t) * vc.unknown.size());
+    const size_t o_out = o_rep + al(n_subsets);
+    HIPCHK(dev.alloc(o_out + sizeof(ValOut) * n_subsets));
+    uint8_t* db = (uint8_t*)dev.p;
+    hipStream_t st = ctx->stream;
+    HIPCHK(hipMemcpyAsync(db, vc.want.data(), sizeof(uint64_t) * vc.want.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(db + o_unk, vc.unknown.data(), sizeof(uint32_t) * vc.unknown.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(db + o_rep, vc.replace.data(), n_subsets, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(db + o_out, 0, sizeof(ValOut) * n_subsets, st));
+    HIPCHK(hipStreamSynchronize(st));  // (the launches run on the batch's own streams)
+    vl.d_want = (const uint64_t*)db;
+    vl.d_unknown = (const uint32_t*)(db + o_unk);
+    vl.d_replace = db + o_rep;
+    vl.d_out = (ValOut*)(db + o_out);
+    static const vector<std::map<string, string>> no_labels;
+    vector<SimOut> no_outs;
+    if (int32_t rc = GeneralBatchRun(plan, gb, cands, batched, no_labels, 0, no_outs, counters, dev_ms, host_ms, cancel,
+                                     &n_launches, nullptr, nullptr, &vl))
+      return rc;
+    vector<ValOut> got(n_subsets);
+    HIPCHK(hipMemcpyAsync(got.data(), vl.d_out, sizeof(ValOut) * n_subsets, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int s : batched)
+      if (!vl.on_host[s]) vl.host_out[s] = got[s];
+  }
+  for (int s : single)
+    if (int32_t rc = ValidateSimOne(plan, cands[s], s, vl, counters, dev_ms, cancel)) return rc;
+  for (uint32_t s = 0; s < n_subsets; s++) {
+    if (blocked[s]) {
+      memset(&vl.host_out[s], 0, sizeof(ValOut));
+      vl.host_out[s].verdict = KP_INVALID_BUDGET;
+      vl.host_out[s].blocked = 1;
+    }
+  }
+  memcpy(out, vl.host_out.data(), sizeof(ValOut) * n_subsets);
+  kst[3] = batched.size(), kst[4] = single.size(), kst[6] = n_launches;
+  return KP_OK;
+}
+
+int32_t kp_cluster_validate(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
+                            uint32_t n_subsets, const kp_command_check* checks, const uint32_t* allowed,
+                            uint32_t n_allowed, kp_validation* out, uint64_t* n_blocked, kp_solve_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (n_blocked) *n_blocked = 0;
+  if (!plan || (n_subsets && (!offsets || !out || !checks))) return fail(KP_E_INVAL, "null argument");
+  if (cancel && cancel->ctx.p != plan->ctx.p) return fail(KP_E_INVAL, "the cancel token belongs to another context");
+  kp_ctx* ctx = plan->ctx;
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  HIPCHK(hipSetDevice(ctx->device));
+  if (stats) memset(stats, 0, sizeof *stats);
+  BudgetGate gate{allowed, n_allowed};
+  BudgetGate* bg = allowed ? &gate : nullptr;
+  if (bg)
+    if (int32_t rc = CheckBudget(plan, bg)) return rc;
+  if (n_subsets == 0) return KP_OK;
+  uint64_t kst[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  float ms = 0;
+  if (plan->general) {
+    uint64_t counters[3] = {0, 0, 0};
+    double dev_ms = 0;
+    gate.blocked = 0;
+    memset(plan->general_phase, 0, sizeof plan->general_phase);
+    if (int32_t rc = ValidateGeneralLocked(plan, cancel, offsets, nodes, n_subsets, checks, bg, out, counters, &dev_ms, kst))
+      return rc;
+    kst[0] = counters[0], kst[1] = counters[1], kst[2] = counters[2];
+    ms = (float)dev_ms;
+  } else {
+    if (int32_t rc = CatalogsAlive(plan->cp->B->alive)) return rc;
+    ValCheck vc;
+    if (int32_t rc = ValidateCompile(plan->cp->B->catalogs, plan->cp->B->TW, checks, n_subsets, vc)) return rc;
+    SimArgs a;
+    if (int32_t rc = SimLaunchLocked(plan, offsets, nodes, n_subsets, 0, a, cancel, bg, nullptr, &vc)) return rc;
+    hipStream_t st = ctx->stream;
+    vector<uint8_t> gbytes(bg ? n_subsets : 0);
+    HIPCHK(hipMemcpyAsync(out, vc.val, sizeof(ValOut) * n_subsets, hipMemcpyDeviceToHost, st));
+    if (bg) HIPCHK(hipMemcpyAsync(gbytes.data(), vc.gate, n_subsets, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(kst, a.stats, sizeof kst, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (kst[5]) return fail(KP_E_CANCELED, "validation simulations cancelled (kp_cancel_set)");
+    HIPCHK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    for (uint32_t s = 0; s < n_subsets; s++) {
+      if (bg && !gbytes[s]) {  // not simulated
+        memset(&out[s], 0, sizeof out[s]);
+        out[s].verdict = KP_INVALID_BUDGET;
+        out[s].blocked = 1;
+      } else if (out[s].n_pods == 0xFFFFFFFFu) {
+        return fail(KP_E_DEVICE, "subset %u overflowed the pod queue", s);
+      }
+    }
+    // NodePool limits: sim_kernel stops where a pod would open a second NodeClaim, judged by the limits the pass began
+    // with. The first NodeClaim has taken its largest option out of its pool's remaining limits (subtractMax), so that
+    // second NodeClaim may no longer exist and the pod fail instead. Such a record is settled by the subset's own
+    // whole Solve (ValidateSimOne); every other record is exact as the kernel left it.
+    bool limited = false;
+    for (uint32_t lp : plan->cp->tmpl_limit_present) limited = limited || lp != 0;
+    if (limited) {
+      if (!plan->cluster()) return fail(KP_E_INVAL, "the plan keeps no cluster");
+      ValRun vl;
+      vl.checks = checks;
+      vl.names.resize(n_subsets);
+      vl.host_out.assign(n_subsets, ValOut{});
+      vl.on_host.assign(n_subsets, 0);
+      uint64_t counters[3] = {0, 0, 0};
+      double dev_ms = 0;
+      for (uint32_t s = 0; s < n_subsets; s++) {
+        if (out[s].verdict != KP_INVALID_MULTIPLE) continue;
+        if (int32_t rc = CheckNames(checks[s], s, vl.names[s])) return rc;
+        const vector<uint32_t> cand(nodes + offsets[s], nodes + offsets[s + 1]);
+        if (int32_t rc = ValidateSimOne(plan, cand, (int)s, vl, counters, &dev_ms, cancel)) return rc;
+        memcpy(&out[s], &vl.host_out[s], sizeof out[s]);
+      }
+      kst[0] += counters[0], kst[1] += counters[1], kst[2] += counters[2];
+      ms += (float)dev_ms;
+    }
+  }
+  if (n_blocked && bg) *n_blocked = gate.blocked;
+  if (stats) {
+    stats->device_ms = ms;
+    stats->solve_kernel_ms = ms;
+    stats->attempts = kst[0];
+    stats->bytes_algorithmic = kst[1];
+    stats->pops = kst[2];
+    stats->phase_cycles[0] = kst[3];
+    if (plan->general) {
+      stats->phase_cycles[1] = kst[4];
+      stats->phase_cycles[2] = kst[6];
+    } else {
+      stats->phase_cycles[1] = plan->sim_waves[0];
+      stats->phase_cycles[2] = plan->sim_waves[1];
+    }
+    stats->prepare_ms = plan->prepare_ms;
+    stats->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
   return KP_OK;
 }
 

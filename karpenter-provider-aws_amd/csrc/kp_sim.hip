@@ -270,6 +270,8 @@ __global__ __launch_bounds__(SIM_WAVES * 64) void sim_prep_kernel(SimArgs a) {
 // GL = SimLive is the gated instantiation (kp_*_budgeted): a.n_subsets counts the admissible subsets and the k-th
 // simulation is subset gl.live[k] (ascending: budget_gate_kernel). GL = SimAll walks every subset; its conditionals on
 // GL::gated fold away before code generation, so that instantiation compiles as it did without the gate.
+// GL = SimCheck (kp_cluster_validate) is gated too and takes no decision: every statement of its own sits under
+// GL::check, which is false in the three other policies, so those are generated from the code they had.
 template <int NW, class GL>
 __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, GL gl) {
   __shared__ DevDict D;
@@ -413,6 +415,10 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
     int head = 0, len = overflow ? 0 : n, n_nc = 0, placed_cnt = 0;
     uint32_t epoch = 1;
     bool abort = overflow;
+    // GL::check (kp_cluster_validate): candidate pods on uninitialized nodes, non-pending pods on the NodeClaim, and
+    // whether the simulation stopped at a second NodeClaim
+    int n_uninit = 0, nc_np = 0;
+    bool multi = false;
     while (len > 0) {
       const int i = ring[head];
       const uint64_t ent = spod[i];
@@ -474,7 +480,10 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
       if (lane == 0) sstart[sl] = st;
       if (placed <= -2) {
         const int e = -2 - placed;
-        if (!a.ex_init[e] && kind == 0) {
+        if constexpr (GL::check) {  // the verdict counts it with the unscheduled pods; the Solve goes on
+          if (!a.ex_init[e] && kind == 0) n_uninit++;
+        }
+        if (!GL::check && !a.ex_init[e] && kind == 0) {
           abort = true;  // SimulateScheduling: a candidate pod relied on an uninitialized node
         } else {
           const bool first = !((dirty[e >> 6] >> (e & 63)) & 1);
@@ -534,6 +543,7 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
       if (placed == -1 && a.tres[sl].tmpl >= 0) {
         if (n_nc == 1) {
           abort = true;
+          if constexpr (GL::check) multi = true;
         } else {
           copy_u64(reinterpret_cast<uint64_t*>(nc), reinterpret_cast<const uint64_t*>(&a.tres[sl]),
                    (int)(sizeof(SimNC) / 8));
@@ -547,6 +557,9 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
       if (abort) break;
       if (placed != -1) {
         if (kind != 2) placed_cnt++;
+        if constexpr (GL::check) {
+          if (placed == 0 && kind != 2) nc_np++;
+        }
         if constexpr (GL::emit) {  // where the pod went, and the NodeClaim's add order
           if (lane == 0) {
             rp[i] = placed;
@@ -578,11 +591,16 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
     int decision = KP_DECISION_NOOP, nodepool = 0, n_options = 0;
     double repl = 0, savings = 0;
     const double candReported = priced ? candPrice : 0.0;
-    if (!abort && placed_cnt == need) {
+    // GL::check: whether the truncated options kept minValues, and the command's options absent from them. The
+    // truncation runs for every finished simulation with a NodeClaim, whatever the candidates' prices and the
+    // spot-to-spot gate say, and no price stage runs.
+    bool v_minok = true;
+    int v_missing = 0;
+    if (!abort && (GL::check || placed_cnt == need)) {
       if (n_nc == 0) {
         decision = KP_DECISION_DELETE;
         savings = candReported;
-      } else if (priced) {
+      } else if (GL::check || priced) {
         const int cat = a.tmpl_catalog[nc->tmpl];
         const DevCatalog& Cg = a.cats[cat];
         const uint64_t v = lane < D.W ? nc->reqs.vals[lane] : 0;
@@ -597,7 +615,7 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
         // spot-to-spot (every candidate spot, the replacement may launch spot): only with the feature gate, on
         // the replacement narrowed to spot offerings, and a single candidate needs 15 cheaper options
         const bool s2s = allSpot && ncSpot;
-        if (!s2s || a.spot_to_spot) {
+        if (GL::check || !s2s || a.spot_to_spot) {
           // TruncateInstanceTypes: OrderByPrice (cheapest compatible offering, then name) + cut
           const uint64_t Xl = lane < D.TW ? nc->X[lane] : 0;
           int cnt = 0;
@@ -637,7 +655,7 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
           uint64_t* msk = s_mask[wave];
           const uint64_t hmin = rv.hmin & rv.present;
           bool ok = true;
-          if (hmin) {  // minValues must survive the truncation, else the pods fail (no-op)
+          if (GL::check || hmin) {  // the truncated list as a type mask (GL::check: the subset test reads it too)
             msk[lane] = 0;
             wave_sync();
             for (int q = lane; q < lim; q += 64) {
@@ -645,111 +663,143 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
               atomicOr((unsigned long long*)&msk[t >> 6], 1ull << (t & 63));
             }
             wave_sync();
+          }
+          if (hmin) {  // minValues must survive the truncation, else the pods fail (no-op)
             ok = minvalues_ok(D, Cg.code, Cg.TM, hmin, rv.minv, lane < D.TW ? msk[lane] : 0, s_scratch[wave]);
           }
-          // filterByPrice: Offerings.Available().WorstLaunchPrice(reqs) < candidate price
-          double wlp[2] = {__DBL_MAX__, __DBL_MAX__};
-          int tt[2] = {-1, -1};
-          for (int h = 0; h < 2; h++) {
-            const int q = h * 64 + lane;
-            if (q >= lim) continue;
-            const int t = (int)(fidx[q] & 4095u);
-            tt[h] = t;
-            for (int pass = 0; pass < (s2s ? 1 : 2); pass++) {  // capacity-type precedence: spot, on-demand
-              const int ctb = pass == 0 ? a.spot_bit : a.od_bit;
-              if (ctb < 0) continue;
-              bool any = false;
-              double mx = 0;
-              uint64_t m = cls;
-              while (m) {
-                const int c = __builtin_ctzll(m);
-                m &= m - 1;
-                if (Cg.cls[c].ct_bit != ctb || !((Cg.offer_avail[(size_t)c * D.TW + (t >> 6)] >> (t & 63)) & 1)) continue;
-                const double pr = Cg.price[(size_t)t * D.C + c];
-                if (!any || pr > mx) mx = pr;
-                any = true;
-              }
-              if (any) {
-                wlp[h] = mx;
-                break;
-              }
-            }
-          }
-          bool keep[2] = {tt[0] >= 0 && wlp[0] < candPrice, tt[1] >= 0 && wlp[1] < candPrice};
-          for (int stage = 0; stage < 2 && ok; stage++) {
-            if (stage == 1) {
-              if (!a.multi_node) break;
-              // filterOutSameType: the cheapest candidate of a kept option's type caps the price
-              double mp = __DBL_MAX__;
-              for (int h = 0; h < 2; h++) {
-                if (!keep[h]) continue;
-                const uint32_t nm = a.type_name[(size_t)cat * D.T + tt[h]];
-                for (int i = 0; i < ns; i++) {
-                  const uint32_t c = a.sub_nodes[s0 + i];
-                  if ((a.node_flags[c] & 1) && a.node_name[c] == nm && a.node_price[c] < mp) mp = a.node_price[c];
+          if constexpr (GL::check) {
+            // the subset test, lane = mask word: the command's types the truncated list lacks (a list that broke
+            // minValues is no list), plus its names this catalogue does not hold
+            const size_t row = (size_t)gl.live[sim] * a.n_catalogs + cat;
+            const uint64_t want = lane < D.TW ? gl.want[row * D.TW + lane] : 0;
+            const uint64_t have = ok && lane < D.TW ? msk[lane] : 0;
+            v_minok = ok;
+            v_missing = wave_sum(__popcll(want & ~have)) + (int)gl.unknown[row];
+          } else {
+            // filterByPrice: Offerings.Available().WorstLaunchPrice(reqs) < candidate price
+            double wlp[2] = {__DBL_MAX__, __DBL_MAX__};
+            int tt[2] = {-1, -1};
+            for (int h = 0; h < 2; h++) {
+              const int q = h * 64 + lane;
+              if (q >= lim) continue;
+              const int t = (int)(fidx[q] & 4095u);
+              tt[h] = t;
+              for (int pass = 0; pass < (s2s ? 1 : 2); pass++) {  // capacity-type precedence: spot, on-demand
+                const int ctb = pass == 0 ? a.spot_bit : a.od_bit;
+                if (ctb < 0) continue;
+                bool any = false;
+                double mx = 0;
+                uint64_t m = cls;
+                while (m) {
+                  const int c = __builtin_ctzll(m);
+                  m &= m - 1;
+                  if (Cg.cls[c].ct_bit != ctb || !((Cg.offer_avail[(size_t)c * D.TW + (t >> 6)] >> (t & 63)) & 1)) continue;
+                  const double pr = Cg.price[(size_t)t * D.C + c];
+                  if (!any || pr > mx) mx = pr;
+                  any = true;
+                }
+                if (any) {
+                  wlp[h] = mx;
+                  break;
                 }
               }
-              const double maxPrice = wave_min_f64(mp);
-              keep[0] = keep[0] && wlp[0] < maxPrice;
-              keep[1] = keep[1] && wlp[1] < maxPrice;
             }
-            const int count = wave_sum((keep[0] ? 1 : 0) + (keep[1] ? 1 : 0));
-            if (hmin) {
-              msk[lane] = 0;
-              wave_sync();
-              for (int h = 0; h < 2; h++)
-                if (keep[h]) atomicOr((unsigned long long*)&msk[tt[h] >> 6], 1ull << (tt[h] & 63));
-              wave_sync();
-              if (!minvalues_ok(D, Cg.code, Cg.TM, hmin, rv.minv, lane < D.TW ? msk[lane] : 0, s_scratch[wave])) ok = false;
+            bool keep[2] = {tt[0] >= 0 && wlp[0] < candPrice, tt[1] >= 0 && wlp[1] < candPrice};
+            for (int stage = 0; stage < 2 && ok; stage++) {
+              if (stage == 1) {
+                if (!a.multi_node) break;
+                // filterOutSameType: the cheapest candidate of a kept option's type caps the price
+                double mp = __DBL_MAX__;
+                for (int h = 0; h < 2; h++) {
+                  if (!keep[h]) continue;
+                  const uint32_t nm = a.type_name[(size_t)cat * D.T + tt[h]];
+                  for (int i = 0; i < ns; i++) {
+                    const uint32_t c = a.sub_nodes[s0 + i];
+                    if ((a.node_flags[c] & 1) && a.node_name[c] == nm && a.node_price[c] < mp) mp = a.node_price[c];
+                  }
+                }
+                const double maxPrice = wave_min_f64(mp);
+                keep[0] = keep[0] && wlp[0] < maxPrice;
+                keep[1] = keep[1] && wlp[1] < maxPrice;
+              }
+              const int count = wave_sum((keep[0] ? 1 : 0) + (keep[1] ? 1 : 0));
+              if (hmin) {
+                msk[lane] = 0;
+                wave_sync();
+                for (int h = 0; h < 2; h++)
+                  if (keep[h]) atomicOr((unsigned long long*)&msk[tt[h] >> 6], 1ull << (tt[h] & 63));
+                wave_sync();
+                if (!minvalues_ok(D, Cg.code, Cg.TM, hmin, rv.minv, lane < D.TW ? msk[lane] : 0, s_scratch[wave])) ok = false;
+              }
+              if (count == 0) ok = false;
+              n_options = count;
             }
-            if (count == 0) ok = false;
-            n_options = count;
-          }
-          if (ok && s2s && ns == 1) {  // MinInstanceTypesForSpotToSpotConsolidation, then the launch keeps 15
-            if (n_options < 15) {
-              ok = false;
-            } else {  // the first 15 (100 with minValues) kept options in price order
-              const int L = hmin ? 100 : 15;
-              const uint64_t lt = (1ull << lane) - 1;
-              const uint64_t b0 = __ballot(keep[0]), b1 = __ballot(keep[1]);
-              keep[0] = keep[0] && __popcll(b0 & lt) < L;
-              keep[1] = keep[1] && __popcll(b0) + __popcll(b1 & lt) < L;
-              n_options = min(n_options, L);
-            }
-          }
-          if (ok) {
-            double b = __DBL_MAX__;
-            for (int h = 0; h < 2; h++)
-              if (keep[h] && wlp[h] < b) b = wlp[h];
-            const double best = wave_min_f64(b);
-            decision = KP_DECISION_REPLACE;
-            nodepool = a.tmpl_nodepool[nc->tmpl];
-            repl = best;
-            savings = candPrice - best;
-            if constexpr (GL::emit) {
-              // the kept options in price order: keep[0..1] compacted over the sorted list, the second 64-lane half
-              // behind the first one's count
-              const uint64_t lt = (1ull << lane) - 1;
-              const uint64_t b0 = __ballot(keep[0]), b1 = __ballot(keep[1]);
-              if (keep[0]) rh->options[__popcll(b0 & lt)] = (uint32_t)tt[0];
-              if (keep[1]) rh->options[__popcll(b0) + __popcll(b1 & lt)] = (uint32_t)tt[1];
-              copy_u64(reinterpret_cast<uint64_t*>(&rh->reqs), reinterpret_cast<const uint64_t*>(&nc->reqs),
-                       (int)(sizeof(KReqs) / 8));
-              if (lane < KP_NRES) rh->requests[lane] = nc->requests[lane];
-              if (lane == 0) {
-                rh->tmpl = nc->tmpl;
-                rh->n_remaining = (uint32_t)cnt;
-                rh->n_kept = (uint32_t)n_options;
-                rh->s2s = s2s ? 1u : 0u;
+            if (ok && s2s && ns == 1) {  // MinInstanceTypesForSpotToSpotConsolidation, then the launch keeps 15
+              if (n_options < 15) {
+                ok = false;
+              } else {  // the first 15 (100 with minValues) kept options in price order
+                const int L = hmin ? 100 : 15;
+                const uint64_t lt = (1ull << lane) - 1;
+                const uint64_t b0 = __ballot(keep[0]), b1 = __ballot(keep[1]);
+                keep[0] = keep[0] && __popcll(b0 & lt) < L;
+                keep[1] = keep[1] && __popcll(b0) + __popcll(b1 & lt) < L;
+                n_options = min(n_options, L);
               }
             }
-          } else {
-            n_options = 0;
+            if (ok) {
+              double b = __DBL_MAX__;
+              for (int h = 0; h < 2; h++)
+                if (keep[h] && wlp[h] < b) b = wlp[h];
+              const double best = wave_min_f64(b);
+              decision = KP_DECISION_REPLACE;
+              nodepool = a.tmpl_nodepool[nc->tmpl];
+              repl = best;
+              savings = candPrice - best;
+              if constexpr (GL::emit) {
+                // the kept options in price order: keep[0..1] compacted over the sorted list, the second 64-lane half
+                // behind the first one's count
+                const uint64_t lt = (1ull << lane) - 1;
+                const uint64_t b0 = __ballot(keep[0]), b1 = __ballot(keep[1]);
+                if (keep[0]) rh->options[__popcll(b0 & lt)] = (uint32_t)tt[0];
+                if (keep[1]) rh->options[__popcll(b0) + __popcll(b1 & lt)] = (uint32_t)tt[1];
+                copy_u64(reinterpret_cast<uint64_t*>(&rh->reqs), reinterpret_cast<const uint64_t*>(&nc->reqs),
+                         (int)(sizeof(KReqs) / 8));
+                if (lane < KP_NRES) rh->requests[lane] = nc->requests[lane];
+                if (lane == 0) {
+                  rh->tmpl = nc->tmpl;
+                  rh->n_remaining = (uint32_t)cnt;
+                  rh->n_kept = (uint32_t)n_options;
+                  rh->s2s = s2s ? 1u : 0u;
+                }
+              }
+            } else {
+              n_options = 0;
+            }
           }
         }
       }
     }
-    if (lane == 0) {
+    if constexpr (GL::check) {
+      // the rule of kp_abi.h (kp_cluster_validate) on this simulation; every lane holds the same six words
+      const uint32_t sub = gl.live[sim];
+      const bool has_repl = gl.replace[sub] != 0;
+      uint32_t verdict = KP_VALID, unsched = 0, missing = 0;
+      if (multi) {
+        verdict = KP_INVALID_MULTIPLE;
+      } else if (!overflow) {
+        unsched = (uint32_t)(need - placed_cnt + n_uninit + (v_minok ? 0 : nc_np));
+        if (unsched) verdict = KP_INVALID_UNSCHEDULED;
+        else if (n_nc == 0) verdict = has_repl ? KP_INVALID_NO_REPLACEMENT_NEEDED : KP_VALID;
+        else if (!has_repl) verdict = KP_INVALID_NEEDS_REPLACEMENT;
+        else if (v_missing) verdict = KP_INVALID_NOT_SUBSET, missing = (uint32_t)v_missing;
+      }
+      const uint32_t w[6] = {verdict, multi ? 2u : (uint32_t)n_nc, overflow ? 0xFFFFFFFFu : (uint32_t)n, unsched, missing, 0u};
+      uint32_t mine = 0;
+#pragma unroll
+      for (int k = 0; k < 6; k++) mine = lane == k ? w[k] : mine;
+      if (lane < 6) gl.val[(size_t)sub * 6 + lane] = mine;
+    }
+    if (!GL::check && lane == 0) {
       SimOut o;
       o.decision = decision;
       o.nodepool = (uint32_t)nodepool;
@@ -803,6 +853,13 @@ hipError_t launch_sim_emit(const SimArgs& a, const SimEmit& em, int n_live, int 
   return hipGetLastError();
 }
 const void* sim_emit_kernel_ptr() { return reinterpret_cast<const void*>(sim_kernel<SIM_WAVES, SimEmit>); }
+hipError_t launch_sim_check(const SimArgs& a, const SimCheck& ck, int n_live, int blocks, size_t dyn_lds, hipStream_t s) {
+  SimArgs al = a;
+  al.n_subsets = n_live;
+  hipLaunchKernelGGL((sim_kernel<SIM_WAVES, SimCheck>), dim3(blocks), dim3(SIM_WAVES * 64), dyn_lds, s, al, ck);
+  return hipGetLastError();
+}
+const void* sim_check_kernel_ptr() { return reinterpret_cast<const void*>(sim_kernel<SIM_WAVES, SimCheck>); }
 const void* sim_kernel_ptr(bool gated) {
   return gated ? reinterpret_cast<const void*>(sim_kernel<SIM_WAVES, SimLive>)
                : reinterpret_cast<const void*>(sim_kernel<SIM_WAVES, SimAll>);
@@ -1025,20 +1082,23 @@ hipError_t launch_budget_gate(const GateArgs& g, hipStream_t s) {
 // deleting node's, 0 a candidate's) and, for a candidate pod on an existing node, that position's "not initialized"
 // bit. The ballot of a 64-position chunk gives the count and - its lowest bit in the first chunk that has one - the
 // first failing position.
-__global__ __launch_bounds__(DRIFT_WAVES * 64) void drift_verdict_kernel(DriftArgs a) {
-  const int lane = LANE;
-  const int j = blockIdx.x * DRIFT_WAVES + (threadIdx.x >> 6);
-  if (j >= a.n) return;  // (wave-uniform)
-  const uint8_t* ar = a.arenas + a.stride * (size_t)j;
-  const int32_t* place = reinterpret_cast<const int32_t*>(ar + a.off_place);
-  const uint64_t* st = reinterpret_cast<const uint64_t*>(ar + a.off_stats);
-  const int32_t* qp = a.qpod + (size_t)j * a.Pc;
-  const int n = max(0, min(a.qlen[j], a.Pc));
+// (The scan is a device function of its own: validate_verdict_kernel shares it. ON_NC also counts the non-pending pods
+// on a new NodeClaim.)
+struct Unscheduled {
+  uint32_t n_bad;  // non-pending pods unscheduled or (candidate pods) on an uninitialized node
+  int first;       // the first such queue position, -1
+  uint32_t nc_np;  // ON_NC: non-pending pods on a new NodeClaim
+};
+template <bool ON_NC>
+__device__ __forceinline__ Unscheduled scan_unscheduled(const DriftArgs& a, const int32_t* place, const int32_t* qp, int n,
+                                                        int lane) {
   uint32_t n_bad = 0;
+  [[maybe_unused]] uint32_t nc_np = 0;
   int first = -1;
   for (int p0 = 0; p0 < n; p0 += 64) {
     const int p = p0 + lane;
     bool bad = false;
+    [[maybe_unused]] bool on_nc = false;
     if (p < n) {
       const int32_t pl = place[p];
       const uint32_t sp = (uint32_t)qp[p];
@@ -1050,6 +1110,7 @@ __global__ __launch_bounds__(DRIFT_WAVES * 64) void drift_verdict_kernel(DriftAr
           const uint32_t pos = (uint32_t)(-(pl + 2));
           bad = pos < (uint32_t)a.n_existing && a.pos_uninit[pos] != 0;
         }
+        if constexpr (ON_NC) on_nc = pl >= 0;
       }
     }
     const uint64_t m = __ballot(bad);
@@ -1057,7 +1118,23 @@ __global__ __launch_bounds__(DRIFT_WAVES * 64) void drift_verdict_kernel(DriftAr
       n_bad += (uint32_t)__builtin_popcountll(m);
       if (first < 0) first = p0 + __builtin_ctzll(m);
     }
+    if constexpr (ON_NC) nc_np += (uint32_t)__builtin_popcountll(__ballot(on_nc));
   }
+  if constexpr (ON_NC) return Unscheduled{n_bad, first, nc_np};
+  else return Unscheduled{n_bad, first, 0u};
+}
+__global__ __launch_bounds__(DRIFT_WAVES * 64) void drift_verdict_kernel(DriftArgs a) {
+  const int lane = LANE;
+  const int j = blockIdx.x * DRIFT_WAVES + (threadIdx.x >> 6);
+  if (j >= a.n) return;  // (wave-uniform)
+  const uint8_t* ar = a.arenas + a.stride * (size_t)j;
+  const int32_t* place = reinterpret_cast<const int32_t*>(ar + a.off_place);
+  const uint64_t* st = reinterpret_cast<const uint64_t*>(ar + a.off_stats);
+  const int32_t* qp = a.qpod + (size_t)j * a.Pc;
+  const int n = max(0, min(a.qlen[j], a.Pc));
+  const Unscheduled u = scan_unscheduled<false>(a, place, qp, n, lane);
+  const uint32_t n_bad = u.n_bad;
+  const int first = u.first;
   if (lane == 0) {
     DriftOut o;
     o.feasible = n_bad == 0 ? 1 : 0;
@@ -1132,5 +1209,127 @@ hipError_t launch_drift_verdict(const DriftArgs& a, hipStream_t s) {
 hipError_t launch_drift_first(const DriftArgs& a, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
   hipLaunchKernelGGL(drift_first_kernel, dim3(1), dim3(DRIFT_FIRST_THREADS), 0, s, a);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Command validation on general-path plans (kp_cluster_validate): behind solve_kernel (consolidation mode: the Solve
+// ends at its second NodeClaim) and finalize_kernel in the launch's stream. validate_verdict_kernel, one wave per
+// simulation, applies the rule of kp_abi.h to the arena: the AllNonPendingPodsScheduled scan drift_verdict_kernel runs
+// (shared), the NodeClaim count from the stats word, and for a single NodeClaim its finalized option list as a type
+// mask in LDS - Truncate's minValues check on it (minvalues_ok on the finalized requirements, as sim_kernel does), then
+// the command's want row of that NodeClaim's catalogue against it. One 24-byte ValOut per simulation at the caller's
+// index, lane w writes word w; validate_sum_kernel folds the launch's counters into one DriftRec (first, local and
+// feasible unused). The launch downloads that record; the verdicts are read once at the end of the call.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(DRIFT_WAVES * 64) void validate_verdict_kernel(ValidateArgs a) {
+  __shared__ DevDict D;
+  __shared__ uint64_t s_mask[DRIFT_WAVES][KP_MAX_TYPE_WORDS];
+  __shared__ uint32_t s_scratch[DRIFT_WAVES][2 * KP_MAX_WORDS];
+  block_copy(D, a.dict);
+  __syncthreads();
+  const int lane = LANE, wave = threadIdx.x >> 6;
+  const int j = blockIdx.x * DRIFT_WAVES + wave;
+  if (j >= a.d.n) return;  // (wave-uniform; no block barrier below)
+  const uint8_t* ar = a.d.arenas + a.d.stride * (size_t)j;
+  const int32_t* place = reinterpret_cast<const int32_t*>(ar + a.d.off_place);
+  const uint64_t* st = reinterpret_cast<const uint64_t*>(ar + a.d.off_stats);
+  const int32_t* qp = a.d.qpod + (size_t)j * a.d.Pc;
+  const int n = max(0, min(a.d.qlen[j], a.d.Pc));
+  const uint32_t sub = (uint32_t)a.d.cidx[j];
+  const Unscheduled u = scan_unscheduled<true>(a.d, place, qp, n, lane);
+  uint32_t n_bad = u.n_bad;
+  const uint32_t nc_np = u.nc_np;
+  const uint32_t n_nc = (uint32_t)st[3];
+  const bool repl = a.replace[sub] != 0;
+  uint32_t verdict = KP_VALID, unsched = 0, missing = 0;
+  if (n_nc > 1) {
+    verdict = KP_INVALID_MULTIPLE;
+  } else {
+    int miss = 0;
+    if (n_nc == 1) {
+      const int32_t tmpl = *reinterpret_cast<const int32_t*>(ar + a.off_nct);
+      const int cat = tmpl >= 0 && tmpl < a.n_tmpl ? a.tmpl_catalog[tmpl] : 0;
+      const int nopt = (int)min(*reinterpret_cast<const uint32_t*>(ar + a.off_nopt), (uint32_t)a.opt_stride);
+      const uint32_t* opts = reinterpret_cast<const uint32_t*>(ar + a.off_opts);
+      uint64_t* msk = s_mask[wave];
+      msk[lane] = 0;
+      wave_sync();
+      for (int q = lane; q < nopt; q += 64) {
+        const uint32_t t = opts[q];
+        if (t < (uint32_t)D.TW * 64u) atomicOr((unsigned long long*)&msk[t >> 6], 1ull << (t & 63));
+      }
+      wave_sync();
+      const KReqs* R = reinterpret_cast<const KReqs*>(ar + a.off_ncr);
+      const uint64_t v = lane < D.W ? R->vals[lane] : 0;
+      const ReqView rv = stored_view(D, R, v);
+      const uint64_t hmin = rv.hmin & rv.present;
+      const DevCatalog& Cg = a.cats[cat];
+      bool ok = true;  // Truncate(reqs, max): minValues must hold on the truncated options, else the NodeClaim's pods fail
+      if (hmin) ok = minvalues_ok(D, Cg.code, Cg.TM, hmin, rv.minv, lane < D.TW ? msk[lane] : 0, s_scratch[wave]);
+      if (!ok) n_bad += nc_np;
+      const size_t row = (size_t)sub * a.n_catalogs + cat;
+      const uint64_t want = lane < D.TW ? a.want[row * D.TW + lane] : 0;
+      const uint64_t have = ok && lane < D.TW ? msk[lane] : 0;
+      miss = wave_sum(__popcll(want & ~have)) + (int)a.unknown[row];
+    }
+    unsched = n_bad;
+    if (unsched) verdict = KP_INVALID_UNSCHEDULED;
+    else if (n_nc == 0) verdict = repl ? KP_INVALID_NO_REPLACEMENT_NEEDED : KP_VALID;
+    else if (!repl) verdict = KP_INVALID_NEEDS_REPLACEMENT;
+    else if (miss) verdict = KP_INVALID_NOT_SUBSET, missing = (uint32_t)miss;
+  }
+  const uint32_t w[6] = {verdict, n_nc > 1 ? 2u : n_nc, (uint32_t)n, unsched, missing, 0u};
+  uint32_t mine = 0;
+#pragma unroll
+  for (int k = 0; k < 6; k++) mine = lane == k ? w[k] : mine;
+  if (lane < 6) reinterpret_cast<uint32_t*>(a.out + sub)[lane] = mine;
+}
+// One block per launch: the Solves' counters, a Solve that exceeded its Queue.Pop bound, the ones that ended on the
+// kp_cancel flag. Every thread folds its simulations in index order and the tree is fixed.
+__global__ __launch_bounds__(DRIFT_FIRST_THREADS) void validate_sum_kernel(ValidateArgs a) {
+  __shared__ int64_t s_run[DRIFT_FIRST_THREADS];
+  __shared__ uint64_t s_sum[4][DRIFT_FIRST_THREADS];
+  const int tid = threadIdx.x;
+  int64_t run = INT64_MAX;
+  uint64_t sum[4] = {0, 0, 0, 0};  // attempts, bytes, pops, cancelled
+  for (int j = tid; j < a.d.n; j += DRIFT_FIRST_THREADS) {
+    const uint64_t* st = reinterpret_cast<const uint64_t*>(a.d.arenas + a.d.stride * (size_t)j + a.d.off_stats);
+    const int64_t c = a.d.cidx[j];
+    if (st[7] != 0 && c < run) run = c;
+    sum[0] += st[0];
+    sum[1] += st[1];
+    sum[2] += st[2];
+    sum[3] += st[46] != 0 ? 1 : 0;
+  }
+  s_run[tid] = run;
+  for (int k = 0; k < 4; k++) s_sum[k][tid] = sum[k];
+  __syncthreads();
+  for (int w = DRIFT_FIRST_THREADS / 2; w > 0; w >>= 1) {
+    if (tid < w) {
+      if (s_run[tid + w] < s_run[tid]) s_run[tid] = s_run[tid + w];
+      for (int k = 0; k < 4; k++) s_sum[k][tid] += s_sum[k][tid + w];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    DriftRec r;
+    r.first = -1;
+    r.local = -1;
+    r.feasible = 0;
+    r.attempts = s_sum[0][0];
+    r.bytes = s_sum[1][0];
+    r.pops = s_sum[2][0];
+    r.runaway = s_run[0] != INT64_MAX ? s_run[0] : -1;
+    r.cancelled = s_sum[3][0];
+    *a.d.rec = r;
+  }
+}
+hipError_t launch_validate_verdict(const ValidateArgs& a, hipStream_t s) {
+  if (a.d.n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(validate_verdict_kernel, dim3((a.d.n + DRIFT_WAVES - 1) / DRIFT_WAVES), dim3(DRIFT_WAVES * 64), 0, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(validate_sum_kernel, dim3(1), dim3(DRIFT_FIRST_THREADS), 0, s, a);
   return hipGetLastError();
 }

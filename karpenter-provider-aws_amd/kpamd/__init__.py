@@ -125,6 +125,9 @@ def load_lib(path=None):
         "kp_cluster_command": (C.c_int32, [C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32), C.c_uint32, C.c_int32,
                                            P(C.c_uint32), C.c_uint32, P(abi.SimResult), P(C.c_void_p), P(C.c_uint64),
                                            P(abi.SolveStats)]),
+        "kp_cluster_validate": (C.c_int32, [C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32), C.c_uint32,
+                                            P(abi.CommandCheck), P(C.c_uint32), C.c_uint32, P(abi.Validation),
+                                            P(C.c_uint64), P(abi.SolveStats)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name, None)
@@ -749,6 +752,38 @@ class ClusterPlan:
         if allowed is not None:
             sd["budget_blocked"] = int(blocked.value)
         return [sim_dict(out[i]) for i in range(n)], commands, sd
+
+    def validate(self, subsets, checks, allowed=None, cancel=None):
+        """kp_cluster_validate on this plan, one prepared from CURRENT state: subsets[s] the candidates of a command
+        (node indices of this plan's cluster), checks[s] what it decided: {"decision": abi.DECISION_DELETE} or
+        {"decision": abi.DECISION_REPLACE, "options": [instance-type names]}. Returns (list of kp_validation dicts,
+        stats); stats gain budget_blocked when allowed (the allowed disruptions per NodePool for the command's
+        reason) is given."""
+        lib = self.ctx.lib
+        if len(checks) != len(subsets):
+            raise ValueError("one check per subset")
+        arena = Arena()
+        offs, flat = abi.subsets_csr(arena, subsets)
+        n = len(subsets)
+        arr = (abi.CommandCheck * max(1, n))()
+        keep = []
+        for s, c in enumerate(checks):
+            names = c.get("options") or []
+            arr[s].decision = int(c["decision"])
+            arr[s].n_options = len(names)
+            if names:
+                buf = (C.c_char_p * len(names))(*[None if x is None else x.encode() for x in names])
+                keep.append(buf)
+                arr[s].options = C.cast(buf, C.POINTER(C.c_char_p))
+        out = (abi.Validation * max(1, n))()
+        blocked, st = C.c_uint64(0), abi.SolveStats()
+        keep_a, ap, na = self._allowed(allowed) if allowed is not None else (None, None, 0)
+        _check(lib, lib.kp_cluster_validate(self.h, cancel.h if cancel is not None else None, offs, flat, n, arr, ap, na,
+                                            out, C.byref(blocked), C.byref(st)))
+        sd = stats_dict(st)
+        if allowed is not None:
+            sd["budget_blocked"] = int(blocked.value)
+        return [{f: int(getattr(out[i], f)) for f, _ in abi.Validation._fields_} for i in range(n)], sd
 
     def close(self):
         if self.h:

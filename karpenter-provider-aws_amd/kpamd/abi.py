@@ -279,6 +279,25 @@ class DriftResult(C.Structure):
                 ("n_unscheduled", C.c_uint32), ("first_unscheduled", C.c_int32), ("blocked", C.c_uint32)]
 
 
+class CommandCheck(C.Structure):
+    """kp_command_check: what a command decided (kp_cluster_validate)."""
+    _fields_ = [("decision", C.c_int32), ("options", C.POINTER(C.c_char_p)), ("n_options", C.c_uint32)]
+
+
+class Validation(C.Structure):
+    """kp_validation: the verdict of one command against the plan's snapshot (kp_cluster_validate)."""
+    _fields_ = [("verdict", C.c_int32), ("n_nodeclaims", C.c_uint32), ("n_pods", C.c_uint32),
+                ("n_unscheduled", C.c_uint32), ("n_missing", C.c_uint32), ("blocked", C.c_uint32)]
+
+
+# enum kp_validity
+(VALID, INVALID_UNSCHEDULED, INVALID_NO_REPLACEMENT_NEEDED, INVALID_MULTIPLE, INVALID_NEEDS_REPLACEMENT,
+ INVALID_NOT_SUBSET, INVALID_BUDGET) = range(7)
+VALIDITY_NAMES = ("KP_VALID", "KP_INVALID_UNSCHEDULED", "KP_INVALID_NO_REPLACEMENT_NEEDED", "KP_INVALID_MULTIPLE",
+                  "KP_INVALID_NEEDS_REPLACEMENT", "KP_INVALID_NOT_SUBSET", "KP_INVALID_BUDGET")
+DECISION_DELETE, DECISION_REPLACE = 1, 2
+
+
 class Choice(C.Structure):
     """kp_choice: the sweep's best decision over all ranks (kp_consolidate_argmin / kp_choice_reduce)."""
     _fields_ = [("subset", C.c_int64), ("counts", C.c_uint64 * 3), ("overflowed", C.c_uint64), ("result", SimResult)]

@@ -26,6 +26,11 @@ CS3 and R:website/content/en/preview/concepts/disruption.md:89-128):
   Controller.compute_command(cluster, plan) one disruption pass in upstream order ("first Drift then Consolidation",
                                             disruption.md:16-27; Emptiness, Drift, MultiNodeConsolidation,
                                             SingleNodeConsolidation): the first method that returns a command wins
+  Validation(cluster, plan)                 Validation.IsValid of a computed command against a FRESH snapshot (upstream
+  Controller.validate(cmd, old, new, plan)  disruption/validation.go, restated in DESIGN §12): the candidates mapped by
+                                            node name (gone, deleting, nominated, the budget walk), then one
+                                            plan.validate (kp_cluster_validate) of the command's decision and options.
+                                            Nothing validates unless asked; Drift commands are not validated.
 
 NodePool disruption budgets (R:website/content/en/preview/concepts/disruption.md:274-333,
 R:pkg/apis/crds/karpenter.sh_nodepools.yaml:95-135), modelled when a NodePool carries `budgets`:
@@ -367,6 +372,86 @@ class Controller:
             c, r = hit
             return self._materialized(plan, "single", [c], r)
         return None
+
+    def validate(self, cmd, old_cluster, cluster, plan, now=None, not_ready=(), extra_deleting=None):
+        """Validation.IsValid of a command computed on old_cluster against the current cluster and its plan: (ok,
+        reason). Nothing calls this unless asked; a Drift command is not validated (upstream runs none on it)."""
+        if cmd.method == "drift":
+            return True, None
+        ok, why, _ = Validation(cluster, plan).validate_command(cmd, old_cluster, now, not_ready, extra_deleting)
+        return ok, why
+
+
+VERDICTS = ("valid", "unscheduled", "no-replacement-needed", "multiple", "needs-replacement", "not-subset", "budget")
+_REASON = {"emptiness": EMPTY, "drift": DRIFTED, "single": UNDERUTILIZED, "multi": UNDERUTILIZED}
+
+
+class Validation:
+    """Validation.IsValid of a consolidation command against a fresh snapshot (upstream disruption/validation.go v1.5.1,
+    restated in DESIGN §12 and include/kp/kp_abi.h: the file is not among the references). cluster / plan: the CURRENT
+    state and its resident snapshot (ClusterPlan, or any object with the same validate(subsets, checks, allowed)).
+    Waiting the consolidation TTL is the caller's; nomination is read from ClusterNode.nominated when present."""
+
+    def __init__(self, cluster, plan):
+        self.cluster, self.plan = cluster, plan
+
+    def allowed(self, cmd, now=None, not_ready=(), extra_deleting=None):
+        """allowed_disruptions for the command's reason, None when no NodePool models budgets."""
+        if not budgets_modelled(self.cluster):
+            return None
+        return allowed_disruptions(self.cluster, _REASON[cmd.method], now, not_ready, extra_deleting)
+
+    def validate_candidates(self, cmd, old_cluster, now=None, not_ready=(), extra_deleting=None):
+        """The command's candidates (indices of old_cluster) mapped by node name into the current cluster: (indices,
+        None), or (None, reason) when one is gone, marked for deletion or nominated, or - with budgets modelled - when
+        the walk over them meets a pool whose allowance for the command's reason is used up."""
+        index = {n.node.name: i for i, n in enumerate(self.cluster.nodes)}
+        mapped = []
+        for c in cmd.candidates:
+            name = old_cluster.nodes[c].node.name
+            i = index.get(name)
+            if i is None:
+                return None, f"candidate {name} is gone"
+            node = self.cluster.nodes[i]
+            if node.deleting:
+                return None, f"candidate {name} is marked for deletion"
+            if getattr(node, "nominated", False):
+                return None, f"candidate {name} is nominated for pending pods"
+            mapped.append(i)
+        allowed = self.allowed(cmd, now, not_ready, extra_deleting)
+        if allowed is not None and len(budget_walk(self.cluster, mapped, allowed)) != len(mapped):
+            return None, f"the {_REASON[cmd.method]} budget no longer allows the command's candidates"
+        return mapped, None
+
+    @staticmethod
+    def option_names(cmd, old_cluster):
+        """The instance-type names of the command's replacement (Command.result["replacements"], a materialized
+        command: Controller(materialize=True)), through the catalogue of the replacement's NodePool in old_cluster."""
+        if cmd.decision != REPLACE:
+            return None
+        repl = cmd.result.get("replacements")
+        if not repl:
+            raise ValueError("a REPLACE command without its replacement: compute it with Controller(materialize=True)")
+        cat = old_cluster.catalogs[old_cluster.nodepools[repl[0]["nodepool"]].catalog]
+        return [cat[int(t)].name for t in repl[0]["options"]]
+
+    def validate_command(self, cmd, old_cluster, now=None, not_ready=(), extra_deleting=None):
+        """(ok, reason, kp_validation dict or None). Emptiness: the candidates pass the candidate check and still
+        carry no reschedulable pods. Single- and multi-node consolidation: the candidate check, then one
+        plan.validate of the mapped candidates with the replacement's options by name."""
+        if cmd.method == "drift":
+            raise ValueError("Drift commands are not validated")
+        mapped, why = self.validate_candidates(cmd, old_cluster, now, not_ready, extra_deleting)
+        if mapped is None:
+            return False, why, None
+        if cmd.method == "emptiness":
+            busy = [self.cluster.nodes[i].node.name for i in mapped if self.cluster.nodes[i].pods]
+            return (False, f"candidate {busy[0]} is no longer empty", None) if busy else (True, None, None)
+        names = self.option_names(cmd, old_cluster)
+        check = {"decision": DELETE} if names is None else {"decision": REPLACE, "options": names}
+        recs, _ = self.plan.validate([mapped], [check], allowed=self.allowed(cmd, now, not_ready, extra_deleting))
+        rec = recs[0]
+        return rec["verdict"] == 0, None if rec["verdict"] == 0 else VERDICTS[rec["verdict"]], rec
 
 
 class _Budgeted:
