@@ -4973,7 +4973,6 @@ int32_t CheckBudget(const kp_cluster_plan* plan, const BudgetGate* bg) {
 
 extern "C" {
 
-struct GeneralBatch;
 static int32_t GeneralBatchBuild(kp_cluster_plan* plan, std::shared_ptr<GeneralBatch>& out);
 // A cluster plan for the general path: the cluster is kept as an owned copy and compiled as the batched simulations'
 // superset Solve (or, where that does not apply, validated by a host compile: every node existing, every pod pending).
@@ -5457,8 +5456,6 @@ double WorstLaunch(const Dict& d, const KReqs& R, const HostType& t, bool spot_o
 }
 }  // namespace
 
-static int32_t SolvePrepare(kp_ctx* ctx, const kp_solve_in* in, kp_comm* comm, kp_solve_plan** out);
-
 // The offerings as OfferAdmits reads them, resolved against one dictionary once (the batched decisions run
 // WorstLaunch over up to 100 options per simulation): per offering its capacity-type class and the dictionary bits
 // of its five offering keys (-1: a value the dictionary lacks, -2: the offering has no such requirement).
@@ -5647,8 +5644,70 @@ struct SimOneSolve {
   std::unique_ptr<kp_solve_plan, void (*)(kp_solve_plan*)> sp{nullptr, kp_solve_plan_destroy};
   std::unique_ptr<kp_solve_result, void (*)(kp_solve_result*)> res{nullptr, kp_result_destroy};
 };
-static int32_t GeneralSolveOne(kp_cluster_plan* plan, const vector<uint32_t>& cand, SimOneSolve& so, uint64_t* counters,
-                               double* dev_ms, kp_cancel* cancel) {
+// What a general-path call adds up over its launches and its subsets compiled alone
+struct GenTotals {
+  uint64_t counters[3] = {0, 0, 0};  // attempts, bytes, pops
+  uint64_t batched = 0, single = 0, n_launches = 0;  // simulations batched / compiled per subset, batched launches
+  double dev_ms = 0;
+  double host_ms[2] = {0, 0};  // the batch's host work: overlays + arguments, decisions
+};
+// The same from the eight counter words a cluster call leaves on the device (sim_kernel's stats, and GeneralSimLocked's
+// in their place: attempts, bytes, pops, batched, single, -, launches) and its device time
+static GenTotals TotalsOf(const uint64_t* kst, double dev_ms) {
+  GenTotals T;
+  for (int k = 0; k < 3; k++) T.counters[k] = kst[k];
+  T.batched = kst[3], T.single = kst[4], T.n_launches = kst[6];
+  T.dev_ms = dev_ms;
+  return T;
+}
+// kp_solve_stats of a cluster call (t0: when the call began). Plans of the batched kernel overwrite phase_cycles[1..2].
+static void FillStats(kp_solve_stats* stats, const kp_cluster_plan* plan, const GenTotals& T,
+                      std::chrono::steady_clock::time_point t0) {
+  stats->device_ms = T.dev_ms;
+  stats->solve_kernel_ms = T.dev_ms;
+  stats->attempts = T.counters[0];
+  stats->bytes_algorithmic = T.counters[1];
+  stats->pops = T.counters[2];
+  stats->phase_cycles[0] = T.batched;
+  stats->phase_cycles[1] = T.single;
+  stats->phase_cycles[2] = T.n_launches;
+  stats->prepare_ms = plan->prepare_ms;
+  stats->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+// AllNonPendingPodsScheduled's rule for one queued pod (the host's copy; the device's is scan_unscheduled). kind: 0 a
+// candidate pod, 1 a deleting node's, 2 pending (never counted). The pod fails unplaced (-1), and a candidate pod also
+// on an existing node (<= -2) that is not initialized (deleting-node pods exempt); initialized(pos) answers for the
+// Solve's existing position pos.
+extern "C++" template <class F>
+static inline bool PodUnscheduled(int kind, int32_t pl, F initialized) {
+  if (kind == 2) return false;
+  return pl == -1 || (kind == 0 && pl <= -2 && !initialized(-2 - pl));
+}
+// SimulateScheduling's Solve over a cluster: its inputs for these existing nodes, queued pods and bound pods
+static kp_solve_in SimulationIn(const kp_cluster& cl, const vector<kp_existing_node>& ex, const vector<kp_pod>& pods,
+                                const vector<kp_bound_pod>& bound) {
+  kp_solve_in in;
+  memset(&in, 0, sizeof in);
+  in.catalogs = cl.catalogs;
+  in.n_catalogs = cl.n_catalogs;
+  in.n_nodepools = cl.n_nodepools;
+  in.nodepools = cl.nodepools;
+  in.existing = ex.data();
+  in.n_existing = (uint32_t)ex.size();
+  in.n_shapes = cl.n_shapes;
+  in.shapes = cl.shapes;
+  in.pods = pods.data();
+  in.n_pods = (uint32_t)pods.size();
+  in.max_instance_types = 100;
+  in.bound_pods = bound.data();
+  in.n_bound_pods = (uint32_t)bound.size();
+  in.namespaces = cl.namespaces;
+  in.n_namespaces = cl.n_namespaces;
+  in.reserved_offering_mode = KP_RESERVED_STRICT;  // SimulateScheduling: NewScheduler(..., DisableReservedCapacityFallback)
+  return in;
+}
+static int32_t GeneralSolveOne(kp_cluster_plan* plan, const vector<uint32_t>& cand, SimOneSolve& so, GenTotals& T,
+                               kp_cancel* cancel) {
   kp_ctx* ctx = plan->ctx;
   const kp_cluster& cl = plan->cluster()->cl;
   const int N = (int)cl.n_nodes;
@@ -5688,24 +5747,7 @@ static int32_t GeneralSolveOne(kp_cluster_plan* plan, const vector<uint32_t>& ca
                        sh.n_required_anti_affinity, 0});
     }
   }
-  kp_solve_in in;
-  memset(&in, 0, sizeof in);
-  in.catalogs = cl.catalogs;
-  in.n_catalogs = cl.n_catalogs;
-  in.n_nodepools = cl.n_nodepools;
-  in.nodepools = cl.nodepools;
-  in.existing = ex.data();
-  in.n_existing = (uint32_t)ex.size();
-  in.n_shapes = cl.n_shapes;
-  in.shapes = cl.shapes;
-  in.pods = pods.data();
-  in.n_pods = (uint32_t)pods.size();
-  in.max_instance_types = 100;
-  in.bound_pods = bound.data();
-  in.n_bound_pods = (uint32_t)bound.size();
-  in.namespaces = cl.namespaces;
-  in.n_namespaces = cl.n_namespaces;
-  in.reserved_offering_mode = KP_RESERVED_STRICT;  // SimulateScheduling: NewScheduler(..., DisableReservedCapacityFallback)
+  const kp_solve_in in = SimulationIn(cl, ex, pods, bound);
   kp_solve_plan* sp = nullptr;
   int32_t rc = SolvePrepare(ctx, &in, nullptr, &sp);
   if (rc) return rc;
@@ -5714,33 +5756,44 @@ static int32_t GeneralSolveOne(kp_cluster_plan* plan, const vector<uint32_t>& ca
   rc = kp_solve_run_cancellable(sp, cancel, &res);
   if (rc) return rc;
   so.res.reset(res);
-  counters[0] += res->stats.attempts;
-  counters[1] += res->stats.bytes_algorithmic;
-  counters[2] += res->stats.pops;
-  *dev_ms += res->stats.device_ms;
+  T.counters[0] += res->stats.attempts;
+  T.counters[1] += res->stats.bytes_algorithmic;
+  T.counters[2] += res->stats.pops;
+  T.dev_ms += res->stats.device_ms;
   return KP_OK;
 }
-static void NarrowToSpot(const Dict& d, KReqs& q);
-// command (kp_cluster_command): where to leave the decision's command, the Solve's own result cut to the options the
-// decision kept; its placements are already in the simulation's input order and name the Solve's existing nodes
-static int32_t GeneralSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand, const vector<std::map<string, string>>& labels,
-                             int32_t multi_node, SimOut& r, uint64_t* counters, double* dev_ms, kp_cancel* cancel,
-                             kp_solve_result** command = nullptr) {
-  SimOneSolve so;
-  if (int32_t rc = GeneralSolveOne(plan, cand, so, counters, dev_ms, cancel)) return rc;
-  const kp_cluster& cl = plan->cluster()->cl;
-  const vector<kp_existing_node>& ex = so.ex;
-  const vector<int>& kind = so.kind;
-  const kp_solve_result* res = so.res.get();
-  r.n_pods = (uint32_t)kind.size();
-  // AllNonPendingPodsScheduled; a candidate pod on an uninitialized node is an error (deleting-node pods exempt)
-  bool all = true;
-  for (size_t p = 0; p < kind.size() && all; p++) {
-    const int32_t pl = res->placement[p];
-    if (kind[p] == 2) continue;
-    if (pl == -1) all = false;
-    else if (kind[p] == 0 && pl <= -2 && !ex[(size_t)(-2 - pl)].initialized) all = false;
+// The spot-to-spot branch of computeConsolidation: the replacement launches spot only, so
+// karpenter.sh/capacity-type In [spot] replaces whatever the NodeClaim required of the capacity type.
+static void NarrowToSpot(const Dict& d, KReqs& q) {
+  const int k = d.key(kCapType);
+  const int bit = k >= 0 ? d.bit(k, "spot") : -1;
+  if (bit < 0) return;
+  for (int wi = 0; wi < nwords(d, k); wi++) q.vals[kw(d, k, wi)] = 0;
+  q.vals[bit / 64] |= 1ull << (bit % 64);
+  q.present |= 1ull << k;
+  q.compl_ &= ~(1ull << k);
+  q.hgt &= ~(1ull << k), q.hlt &= ~(1ull << k), q.hmin &= ~(1ull << k);
+}
+// A command (kp_cluster_command) is the Solve's own result cut to the options the decision kept, spot-to-spot narrowed
+static void CutToCommand(const Dict& d, kp_solve_result& res, const vector<int>& kept, bool s2s) {
+  res.ncs[0].options.assign(kept.begin(), kept.end());
+  if (s2s) {
+    NarrowToSpot(d, res.fin[0]);
+    res.ncs[0].reqs = DecodeReqs(d, res.fin[0]);
   }
+}
+// command (kp_cluster_command): where to leave the decision's command; its placements are already in the simulation's
+// input order and name the Solve's existing nodes
+static int32_t GeneralSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand, const vector<std::map<string, string>>& labels,
+                             int32_t multi_node, SimOut& r, GenTotals& T, kp_cancel* cancel, kp_solve_result** command) {
+  SimOneSolve so;
+  if (int32_t rc = GeneralSolveOne(plan, cand, so, T, cancel)) return rc;
+  const kp_cluster& cl = plan->cluster()->cl;
+  const kp_solve_result* res = so.res.get();
+  r.n_pods = (uint32_t)so.kind.size();
+  bool all = true;  // (a no-op at the first failure)
+  for (size_t p = 0; p < so.kind.size() && all; p++)
+    all = !PodUnscheduled(so.kind[p], res->placement[p], [&](int pos) { return so.ex[(size_t)pos].initialized != 0; });
   const int n_nc = (int)res->ncs.size();
   vector<int> kept;
   bool s2s = false;
@@ -5749,15 +5802,8 @@ static int32_t GeneralSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand
                 n_nc ? res->ncs[0].nodepool : 0, n_nc ? res->ncs[0].options.data() : nullptr,
                 n_nc ? (uint32_t)res->ncs[0].options.size() : 0, multi_node, r, nullptr, nullptr, &kept, &s2s);
   if (command && r.decision != KP_DECISION_NOOP) {
-    kp_solve_result* cr = so.res.release();
-    if (r.decision == KP_DECISION_REPLACE) {
-      cr->ncs[0].options.assign(kept.begin(), kept.end());
-      if (s2s) {
-        NarrowToSpot(so.sp->cp->B->d, cr->fin[0]);
-        cr->ncs[0].reqs = DecodeReqs(so.sp->cp->B->d, cr->fin[0]);
-      }
-    }
-    *command = cr;
+    if (r.decision == KP_DECISION_REPLACE) CutToCommand(so.sp->cp->B->d, *so.res, kept, s2s);
+    *command = so.res.release();
   }
   return KP_OK;
 }
@@ -5806,11 +5852,13 @@ struct PinnedBuf {
 struct GenSlot {
   DevBuf arenas, args;
   size_t arenas_bytes = 0, args_bytes = 0;
-  DevBuf drift;  // drift launches: the simulations' queue pods, lengths and caller indices, and the launch's record
-  size_t drift_bytes = 0;
+  DevBuf rec;  // record-mode launches: the simulations' queue pods, lengths and caller indices, and the launch's record
+  size_t rec_bytes = 0;
   PinnedBuf up, down;
   hipEvent_t done = nullptr, t0 = nullptr, t1 = nullptr;  // results landed; the launch's kernels (timing)
   hipEvent_t uploaded = nullptr;                            // the launch's overlays and arguments on the device
+  hipStream_t ks = nullptr;               // the slot's kernel stream (CopyStreams::k)
+  const FinalizeArgs* dfargs = nullptr;   // the launch's finalize arguments in `args`
   int n = 0;
   size_t b0 = 0;
   vector<vector<int32_t>> queues;
@@ -5860,10 +5908,10 @@ struct GeneralBatch {
   DevBuf pristine;
   GenSlot slot[2];  // two launch slots (GeneralBatchRun)
   CopyStreams cs;
-  // kp_cluster_drift: what drift_verdict_kernel gathers, uploaded once per plan (DriftTables), and the verdicts
+  // what the verdict kernels gather, uploaded once per plan (RecordTables), and kp_cluster_drift's verdicts
   vector<int32_t> pod_cluster;  // superset pod -> cluster pod index
   bool min_values = false;      // some template or shape-level carries minValues (drift: the per-subset path)
-  DevBuf drift_tab, drift_out;
+  DevBuf rec_tab, drift_out;
   size_t drift_out_n = 0;
   const uint8_t* d_pod_kind = nullptr;
   const int32_t* d_pod_cluster = nullptr;
@@ -5920,24 +5968,7 @@ static int32_t GeneralBatchBuild(kp_cluster_plan* plan, std::shared_ptr<GeneralB
     if (std::adjacent_find(keys.begin(), keys.end()) != keys.end())
       return fail(KP_E_UNSUPPORTED, "pods with equal (creation, UID) keys");
   }
-  kp_solve_in in;
-  memset(&in, 0, sizeof in);
-  in.catalogs = cl.catalogs;
-  in.n_catalogs = cl.n_catalogs;
-  in.n_nodepools = cl.n_nodepools;
-  in.nodepools = cl.nodepools;
-  in.existing = ex.data();
-  in.n_existing = (uint32_t)ex.size();
-  in.n_shapes = cl.n_shapes;
-  in.shapes = cl.shapes;
-  in.pods = pods.data();
-  in.n_pods = (uint32_t)pods.size();
-  in.max_instance_types = 100;
-  in.bound_pods = bound.data();
-  in.n_bound_pods = (uint32_t)bound.size();
-  in.namespaces = cl.namespaces;
-  in.n_namespaces = cl.n_namespaces;
-  in.reserved_offering_mode = KP_RESERVED_STRICT;
+  const kp_solve_in in = SimulationIn(cl, ex, pods, bound);
   pt.lap("general: inputs");
   gb->C = std::make_unique<Compiled>();
   Compiled& C = *gb->C;
@@ -6161,40 +6192,489 @@ static int GeneralPatch(const GeneralBatch& gb, const kp_cluster& cl, const vect
   return 0;
 }
 
-// kp_cluster_drift's state across the launches of one call (GeneralBatchRun in drift mode, DriftSimOne)
-struct DriftRun {
-  vector<DriftOut> host_out;  // caller order: the verdicts taken on the host (subsets compiled on their own) ...
-  vector<char> on_host;       // ... and which entries those are; the rest come from the device array
-  DriftOut* d_out = nullptr;  // [n_subsets] drift_verdict_kernel's verdicts, caller order
-  int64_t first = -1;         // the lowest feasible caller-order subset so far
-  std::unique_ptr<kp_solve_result> res;  // its Solve result
+// The verdict kernels' gathers (drift_verdict_kernel, validate_verdict_kernel), uploaded once per superset Solve: pod
+// kind and cluster pod per superset pod, the "not initialized" byte per existing position
+static int32_t RecordTables(kp_ctx* ctx, GeneralBatch& gb, const kp_cluster& cl) {
+  if (gb.rec_tab.p) return KP_OK;
+  const size_t P = gb.pod_kind.size(), E = gb.pos_node.size();
+  const size_t o_cl = (P + 255) & ~(size_t)255, o_un = (o_cl + sizeof(int32_t) * P + 255) & ~(size_t)255;
+  vector<uint8_t> h(o_un + std::max<size_t>(E, 1), 0);
+  if (P) memcpy(h.data(), gb.pod_kind.data(), P);
+  if (P) memcpy(h.data() + o_cl, gb.pod_cluster.data(), sizeof(int32_t) * P);
+  for (size_t e = 0; e < E; e++) h[o_un + e] = cl.nodes[gb.pos_node[e]].node.initialized ? 0 : 1;
+  HIPCHK(gb.rec_tab.alloc(h.size()));
+  HIPCHK(hipMemcpyAsync(gb.rec_tab.p, h.data(), h.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const uint8_t* d = (const uint8_t*)gb.rec_tab.p;
+  gb.d_pod_kind = d;
+  gb.d_pod_cluster = reinterpret_cast<const int32_t*>(d + o_cl);
+  gb.d_pos_uninit = d + o_un;
+  return KP_OK;
+}
+
+// The simulation's input order and existing-node index, as kp_abi.h states them for kp_cluster_drift's replacements and
+// kp_cluster_command's commands: pending pods, the deleting nodes' pods in node order, the subset's pods in subset
+// order; the nodes neither in the subset nor being deleted, in cluster order.
+struct CommandIndex {
+  const kp_cluster& cl;
+  vector<int32_t> pod_idx;     // [P] input index of a queued pod, -1
+  vector<int32_t> del_before;  // [N + 1] deleting nodes before node i
+  vector<uint32_t> sorted;     // the current subset's nodes, ascending
+  vector<uint32_t> cand_pods;
+  int n_base = 0;
+  explicit CommandIndex(const kp_cluster& c) : cl(c), pod_idx(std::max<uint32_t>(c.n_pods, 1), -1), del_before(c.n_nodes + 1, 0) {
+    for (uint32_t j = 0; j < cl.n_pending; j++) pod_idx[cl.pending_pods[j]] = n_base++;
+    for (uint32_t i = 0; i < cl.n_nodes; i++) {
+      del_before[i + 1] = del_before[i] + (cl.nodes[i].deleting ? 1 : 0);
+      if (cl.nodes[i].deleting)
+        for (uint32_t j = 0; j < cl.nodes[i].n_pods; j++) pod_idx[cl.nodes[i].pods[j]] = n_base++;
+    }
+  }
+  int Enter(const uint32_t* cand, uint32_t n) {  // -> pods queued
+    sorted.assign(cand, cand + n);
+    std::sort(sorted.begin(), sorted.end());
+    int k = n_base;
+    for (uint32_t i = 0; i < n; i++)
+      for (uint32_t j = 0; j < cl.nodes[cand[i]].n_pods; j++) {
+        cand_pods.push_back(cl.nodes[cand[i]].pods[j]);
+        pod_idx[cand_pods.back()] = k++;
+      }
+    return k;
+  }
+  void Leave() {
+    for (uint32_t p : cand_pods) pod_idx[p] = -1;
+    cand_pods.clear();
+  }
+  int Existing(uint32_t node) const {  // -1: in the subset or being deleted
+    if (node >= cl.n_nodes || cl.nodes[node].deleting) return -1;
+    auto it = std::lower_bound(sorted.begin(), sorted.end(), node);
+    if (it != sorted.end() && *it == node) return -1;
+    return (int)node - del_before[node] - (int)(it - sorted.begin());
+  }
 };
-static int32_t DriftSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand, int s, DriftRun& dr, uint64_t* counters,
-                           double* dev_ms, kp_cancel* cancel);
-// kp_cluster_validate's state across the launches of one call (GeneralBatchRun in validation mode, ValidateSimOne)
-struct ValRun {
-  const kp_command_check* checks = nullptr;
-  vector<vector<string>> names;  // per subset: the check's names as a set
-  vector<ValOut> host_out;       // caller order: the verdicts taken on the host (subsets compiled on their own) ...
-  vector<char> on_host;          // ... and which entries those are; the rest come from the device array
-  ValOut* d_out = nullptr;       // [n_subsets] validate_verdict_kernel's records, caller order
-  const uint64_t* d_want = nullptr;
+
+// The Solve result of simulation j of a finished launch, read from its arena (still resident: the slot is reused by
+// the launch after the next, which is not queued yet): what kp_solve_run copies back, in the indices of
+// kp_cluster_drift's replacements and kp_cluster_command's commands (pods in the simulation's input order, existing
+// nodes among those neither in the subset nor being deleted).
+static int32_t ArenaSolveResult(kp_cluster_plan* plan, GeneralBatch& gb, const GenSlot& sl, int j, const vector<uint32_t>& cand,
+                                std::unique_ptr<kp_solve_result>& out) {
+  kp_ctx* ctx = plan->ctx;
+  const kp_cluster& cl = plan->cluster()->cl;
+  const Compiled& C = *gb.C;
+  const SolveOffs& o = gb.o;
+  const int Pc = gb.Pc, opt_stride = gb.opt_stride;
+  const uint8_t* ar = (const uint8_t*)sl.arenas.p + gb.stride * (size_t)j;
+  const vector<int32_t>& q = sl.queues[j];
+  hipStream_t st = ctx->stream;
+  uint64_t stats[KP_SOLVE_STATS];
+  HIPCHK(hipMemcpyAsync(stats, ar + o.stats, sizeof stats, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const int P = (int)q.size();
+  if (P > Pc) return fail(KP_E_DEVICE, "drift result: %d pods in an arena of %d", P, Pc);
+  ArenaResult a;
+  const ResultOffs ro{o.place, o.events, o.nct, o.ncrq, o.opts, o.nrem, o.nopt, o.ncr, o.held};
+  if (int32_t rc = FetchArenaResult(st, ar, ro, Pc, opt_stride, gb.res_mode != 0, (int)stats[3], a)) return rc;
+  CommandIndex ix(cl);  // (queue position -> superset pod -> cluster pod -> input index)
+  ix.Enter(cand.data(), (uint32_t)cand.size());
+  auto res = std::make_unique<kp_solve_result>();
+  if (int32_t rc = AssembleResult(*C.B, stats, a, P, opt_stride, [&](int p) { return ix.pod_idx[gb.pod_cluster[q[p]]]; },
+                                  [&](int pos) { return pos < (int)gb.pos_node.size() ? ix.Existing((uint32_t)gb.pos_node[pos]) : -1; }, *res))
+    return rc;
+  memset(&res->stats, 0, sizeof res->stats);
+  res->stats.attempts = stats[0];
+  res->stats.bytes_algorithmic = stats[1];
+  res->stats.pops = stats[2];
+  res->stats.scanned = stats[5];
+  res->stats.cursor_starts = stats[6];
+  res->stats.prepare_ms = plan->prepare_ms;
+  out = std::move(res);
+  return KP_OK;
+}
+
+// ---- the launch loop (GeneralBatchRun) and its result modes: consolidation decisions and commands, drift verdicts,
+// the validation of commands ------------------------------------------------------------------------------------
+// What one GeneralBatchRun call fixes before its first launch, and its host argument blocks
+struct GenRun {
+  GeneralBatch& gb;
+  const vector<vector<uint32_t>>& cands;
+  vector<int> order;   // the call's subsets, longest simulations first; a launch takes order[b0 .. b0 + n)
+  vector<size_t> len;  // per subset: the pods it queues
+  int Pc = 64;            // the arena size in pods
+  size_t per_launch = 1;  // simulations per launch
+  hipStream_t up = nullptr, dn = nullptr;  // the copy streams
+  vector<SolveArgs> sargs;                 // the launch being queued: [0] holds the tables every simulation shares
+  vector<FinalizeArgs> fargs;
+  // a consolidation launch's results in the slot's pinned download buffer
+  size_t r_stats = 0, r_place = 0, r_nct = 0, r_nopt = 0, r_opts = 0, r_fin = 0, r_held = 0, r_end = 0;
+  // the slot's pinned upload buffer: overlays, the two argument blocks, the record-modes' mirror of the record buffer
+  size_t u_args = 0, u_fargs = 0, u_end = 0, u_rec = 0;
+  // the slot's record buffer: queue pods [n][Pc], lengths [n], caller indices [n], then the record
+  size_t d_qlen = 0, d_cidx = 0, d_rec = 0;
+};
+// The hooks run in this order for a launch on slot sl (which holds its n, b0, kernel stream and device arguments)
+struct GeneralMode {
+  kp_cluster_plan* plan;
+  GenTotals& T;
+  kp_cancel* cancel;
+  int32_t stop_nc;  // SolveArgs::stop_nc: the NodeClaim count that ends a simulation's Solve (0: the whole Solve)
+  GeneralMode(kp_cluster_plan* p, GenTotals& t, kp_cancel* c, int32_t stop) : plan(p), T(t), cancel(c), stop_nc(stop) {}
+  virtual ~GeneralMode() = default;
+  virtual hipError_t Reserve(const GenRun& R, GenSlot& sl) = 0;      // the slot's pinned buffers (and the mode's own), sized
+  virtual int32_t Upload(const GenRun&, GenSlot&) { return KP_OK; }  // the mode's uploads, on R.up behind the arguments
+  virtual int32_t Enqueue(const GenRun& R, GenSlot& sl) = 0;         // its kernels, on sl.ks behind launch_solve_batch
+  virtual int32_t Download(const GenRun& R, GenSlot& sl) = 0;        // its downloads into sl.down, on R.dn
+  // the launch has finished: its results are in sl.down, its arenas resident until the launch after the next is queued
+  virtual int32_t Decide(const GenRun& R, GenSlot& sl) = 0;
+  // subset s compiled and solved on its own (not batchable, or no room for the arenas)
+  virtual int32_t SimOne(const vector<uint32_t>& cand, int s) = 0;
+};
+
+// kp_cluster_simulate / kp_cluster_command: the decision per subset on the host, from the launch's downloaded results;
+// commands (or null): the command of every subset that decided DELETE or REPLACE
+struct ConsolidateMode final : GeneralMode {
+  const vector<std::map<string, string>>& labels;
+  int32_t multi_node;
+  vector<SimOut>& outs;
+  kp_solve_result** commands;
+  ConsolidateMode(kp_cluster_plan* p, GenTotals& t, kp_cancel* c, const vector<std::map<string, string>>& l, int32_t mn,
+                  vector<SimOut>& o, kp_solve_result** cmds)
+      : GeneralMode(p, t, c, 2), labels(l), multi_node(mn), outs(o), commands(cmds) {}  // (a second NodeClaim: no-op)
+  hipError_t Reserve(const GenRun& R, GenSlot& sl) override {
+    const hipError_t e = sl.up.reserve(R.u_end);
+    return e != hipSuccess ? e : sl.down.reserve(R.r_end);
+  }
+  int32_t Enqueue(const GenRun& R, GenSlot& sl) override {
+    HIPCHK(launch_finalize_batch(R.fargs[0], sl.dfargs, sl.n, sl.ks));
+    return KP_OK;
+  }
+  int32_t Download(const GenRun& R, GenSlot& sl) override {
+    const GeneralBatch& gb = R.gb;
+    const SolveOffs& o = gb.o;
+    auto down = [&](size_t roff, size_t off, size_t width) {
+      return hipMemcpy2DAsync(sl.down.at(roff), width, (const uint8_t*)sl.arenas.p + off, gb.stride, width, sl.n,
+                              hipMemcpyDeviceToHost, R.dn);
+    };
+    HIPCHK(down(R.r_stats, o.stats, sizeof(uint64_t) * KP_SOLVE_STATS));
+    HIPCHK(down(R.r_place, o.place, sizeof(int32_t) * R.Pc));
+    HIPCHK(down(R.r_nct, o.nct, sizeof(int32_t)));
+    HIPCHK(down(R.r_nopt, o.nopt, sizeof(uint32_t)));
+    HIPCHK(down(R.r_opts, o.opts, sizeof(uint32_t) * gb.opt_stride));
+    HIPCHK(down(R.r_fin, o.ncr, sizeof(KReqs)));
+    if (gb.res_mode) HIPCHK(down(R.r_held, o.held, sizeof(uint64_t)));
+    return KP_OK;
+  }
+  int32_t Decide(const GenRun& R, GenSlot& sl) override {
+    GeneralBatch& gb = R.gb;
+    const Compiled& C = *gb.C;
+    const kp_cluster& cl = plan->cluster()->cl;
+    const int n = sl.n, Pc = R.Pc;
+    const size_t b0 = sl.b0;
+    const uint64_t* stats = reinterpret_cast<uint64_t*>(sl.down.at(R.r_stats));
+    const int32_t* place = reinterpret_cast<int32_t*>(sl.down.at(R.r_place));
+    const int32_t* nct = reinterpret_cast<int32_t*>(sl.down.at(R.r_nct));
+    const uint32_t* nopt = reinterpret_cast<uint32_t*>(sl.down.at(R.r_nopt));
+    uint32_t* opts = reinterpret_cast<uint32_t*>(sl.down.at(R.r_opts));
+    const KReqs* fin = reinterpret_cast<KReqs*>(sl.down.at(R.r_fin));
+    const uint64_t* held = reinterpret_cast<uint64_t*>(sl.down.at(R.r_held));
+    std::atomic<int> bad_runaway{-1}, cancelled{0};
+    uint64_t tcount[kMaxHostThreads][3] = {}, tphase[kMaxHostThreads][8] = {};
+    // kp_cluster_command: the options each decision kept and whether it was taken as spot-to-spot
+    vector<vector<int>> keptv(commands ? n : 0);
+    vector<uint8_t> s2sv(commands ? n : 0, 0);
+    ParallelFor(n, [&](int j_lo, int j_hi, int t) {
+    for (int j = j_lo; j < j_hi; j++) {
+      const int i = R.order[b0 + j];
+      const uint64_t* sj = &stats[(size_t)j * KP_SOLVE_STATS];
+      if (sj[7]) {
+        bad_runaway = i;
+        return;
+      }
+      if (sj[46]) {
+        cancelled = 1;
+        return;
+      }
+      for (int k = 0; k < 3; k++) tcount[t][k] += sj[k];
+      for (int k = 0; k < 8; k++) tphase[t][k] += sj[8 + k];  // (zero unless kp_overrides.timing)
+      const int n_nc = (int)sj[3];
+      const vector<int32_t>& q = sl.queues[j];
+      SimOut& out = outs[i];
+      out.n_pods = (uint32_t)q.size();
+      bool all = true;  // (a no-op at the first failure)
+      for (size_t p = 0; p < q.size() && all; p++)
+        all = !PodUnscheduled(gb.pod_kind[q[p]], place[(size_t)j * Pc + p],
+                              [&](int pos) { return cl.nodes[gb.pos_node[pos]].node.initialized != 0; });
+      KReqs Rq = fin[j];
+      int ci = 0;
+      uint32_t np = 0;
+      if (n_nc == 1) {
+        if (gb.res_mode) ApplyHeld(*C.B, held[j], Rq);
+        ci = C.B->tmpl_catalog[nct[j]];
+        np = (uint32_t)C.B->tmpl_nodepool[nct[j]];
+      }
+      bool s2s = false;
+      GeneralDecide(cl, labels, R.cands[i], *C.B, all, n_nc, &Rq, ci, np, &opts[(size_t)j * gb.opt_stride],
+                    n_nc == 1 ? nopt[j] : 0, multi_node, out, &gb.offers, &gb.cands, commands ? &keptv[j] : nullptr, &s2s);
+      if (commands) s2sv[j] = s2s ? 1 : 0;
+    }
+    });
+    for (int t = 0; t < kMaxHostThreads; t++) {
+      for (int k = 0; k < 3; k++) T.counters[k] += tcount[t][k];
+      for (int k = 0; k < 8; k++) plan->general_phase[k] += tphase[t][k];
+    }
+    if (bad_runaway >= 0)
+      return fail(KP_E_DEVICE, "solve_kernel exceeded its Queue.Pop bound in simulation %d: aborted", bad_runaway.load());
+    if (cancelled) return fail(KP_E_CANCELED, "consolidation simulations cancelled (kp_cancel_set)");
+    // kp_cluster_command: the command of every simulation that decided DELETE or REPLACE, from its arena while the
+    // slot still holds it, as drift reads its winner (ArenaSolveResult), then cut to the options the decision kept. A
+    // simulation that stopped at its second NodeClaim decided no-op and is not read.
+    for (int j = 0; commands && j < n; j++) {
+      const int i = R.order[b0 + j];
+      if (outs[i].decision == KP_DECISION_NOOP) continue;
+      std::unique_ptr<kp_solve_result> res;
+      if (int32_t rc = ArenaSolveResult(plan, gb, sl, j, R.cands[i], res)) return rc;
+      const bool replace = outs[i].decision == KP_DECISION_REPLACE;
+      if (res->ncs.size() != (replace ? 1u : 0u))
+        return fail(KP_E_DEVICE, "command of subset %d: %zu NodeClaims in its arena", i, res->ncs.size());
+      if (replace) CutToCommand(C.B->d, *res, keptv[j], s2sv[j] != 0);
+      commands[i] = res.release();
+    }
+    return KP_OK;
+  }
+  int32_t SimOne(const vector<uint32_t>& cand, int s) override {
+    return GeneralSimOne(plan, cand, labels, multi_node, outs[s], T, cancel, commands ? &commands[s] : nullptr);
+  }
+};
+
+// Per-subset verdicts of a record-mode call, caller order: the device array the launches' kernels write, and the
+// entries taken on the host instead (subsets compiled on their own)
+extern "C++" template <class Out>
+struct Verdicts {
+  vector<Out> host;
+  vector<char> on_host;
+  Out* dev = nullptr;  // [n_subsets]
+  explicit Verdicts(uint32_t n) : host(n, Out{}), on_host(n, 0) {}
+  Out& OnHost(int s) {
+    on_host[s] = 1;
+    return host[s];
+  }
+  // the verdicts of every launch: one copy (the launches have drained: their records were read); the host's entries stay
+  int32_t Merge(hipStream_t st, const vector<int>& batched) {
+    vector<Out> got(host.size());
+    HIPCHK(hipMemcpyAsync(got.data(), dev, sizeof(Out) * got.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int s : batched)
+      if (!on_host[s]) host[s] = got[s];
+    return KP_OK;
+  }
+  // the call's answer: the budget-blocked subsets (never simulated) get `stamp`
+  void Emit(const vector<char>& blocked, const Out& stamp, void* out) {
+    for (size_t s = 0; s < host.size(); s++)
+      if (blocked[s]) host[s] = stamp;
+    if (out && !host.empty()) memcpy(out, host.data(), sizeof(Out) * host.size());
+  }
+};
+
+// Drift and validation: the verdicts stay on the device (Verdicts::dev) and a launch downloads one record. The slot's
+// record buffer holds the simulations' queue pods [n][Pc], lengths [n] and caller indices [n], then the record; the
+// upload buffer mirrors it behind the arguments. (DriftArgs / DriftRec: kp_device.h's names for the record-mode
+// arguments and the launch's record, whichever mode fills them.)
+struct RecordMode : GeneralMode {
+  const char* what;  // the cancellation message's word
+  DriftArgs da;      // the launch being queued (Upload fills it; Enqueue and Download read it)
+  RecordMode(kp_cluster_plan* p, GenTotals& t, kp_cancel* c, int32_t stop, const char* w) : GeneralMode(p, t, c, stop), what(w) {}
+  hipError_t Reserve(const GenRun& R, GenSlot& sl) override {
+    hipError_t e = sl.up.reserve(R.u_rec + R.d_rec);
+    if (e == hipSuccess) e = sl.down.reserve(sizeof(DriftRec));
+    if (e == hipSuccess && sl.rec_bytes < R.d_rec + sizeof(DriftRec)) {
+      e = sl.rec.alloc(R.d_rec + sizeof(DriftRec));
+      sl.rec_bytes = e == hipSuccess ? R.d_rec + sizeof(DriftRec) : 0;
+    }
+    return e;
+  }
+  int32_t Upload(const GenRun& R, GenSlot& sl) override {
+    const GeneralBatch& gb = R.gb;
+    const int n = sl.n, Pc = R.Pc;
+    uint8_t* hd = sl.up.at(R.u_rec);
+    uint8_t* dd = (uint8_t*)sl.rec.p;
+    int32_t* qpod = reinterpret_cast<int32_t*>(hd);
+    int32_t* qlen = reinterpret_cast<int32_t*>(hd + R.d_qlen);
+    int32_t* cidx = reinterpret_cast<int32_t*>(hd + R.d_cidx);
+    for (int j = 0; j < n; j++) {
+      const vector<int32_t>& q = sl.queues[j];
+      memcpy(qpod + (size_t)j * Pc, q.data(), sizeof(int32_t) * q.size());
+      qlen[j] = (int32_t)q.size();
+      cidx[j] = R.order[sl.b0 + j];
+    }
+    HIPCHK(hipMemcpyAsync(dd, hd, sizeof(int32_t) * (size_t)Pc * n, hipMemcpyHostToDevice, R.up));
+    HIPCHK(hipMemcpyAsync(dd + R.d_qlen, hd + R.d_qlen, sizeof(int32_t) * n, hipMemcpyHostToDevice, R.up));
+    HIPCHK(hipMemcpyAsync(dd + R.d_cidx, hd + R.d_cidx, sizeof(int32_t) * n, hipMemcpyHostToDevice, R.up));
+    memset(&da, 0, sizeof da);
+    da.n = n;
+    da.Pc = Pc;
+    da.n_existing = (int32_t)gb.C->ex_input.size();
+    da.n_super = (int32_t)gb.pod_kind.size();
+    da.arenas = (uint8_t*)sl.arenas.p;
+    da.stride = gb.stride;
+    da.off_place = gb.o.place;
+    da.off_stats = gb.o.stats;
+    da.qpod = reinterpret_cast<const int32_t*>(dd);
+    da.qlen = reinterpret_cast<const int32_t*>(dd + R.d_qlen);
+    da.cidx = reinterpret_cast<const int32_t*>(dd + R.d_cidx);
+    da.pod_kind = gb.d_pod_kind;
+    da.pod_cluster = gb.d_pod_cluster;
+    da.pos_uninit = gb.d_pos_uninit;
+    da.rec = reinterpret_cast<DriftRec*>(dd + R.d_rec);
+    return KP_OK;
+  }
+  int32_t Download(const GenRun& R, GenSlot& sl) override {  // the record only (the verdicts: Verdicts::Merge)
+    HIPCHK(hipMemcpyAsync(sl.down.at(0), da.rec, sizeof(DriftRec), hipMemcpyDeviceToHost, R.dn));
+    return KP_OK;
+  }
+  static const DriftRec& Record(const GenSlot& sl) { return *reinterpret_cast<const DriftRec*>(sl.down.at(0)); }
+  int32_t Decide(const GenRun&, GenSlot& sl) override {  // the launch's record: counters, a runaway Solve, cancellation
+    const DriftRec& rec = Record(sl);
+    T.counters[0] += rec.attempts;
+    T.counters[1] += rec.bytes;
+    T.counters[2] += rec.pops;
+    if (rec.runaway >= 0)
+      return fail(KP_E_DEVICE, "solve_kernel exceeded its Queue.Pop bound in simulation %lld: aborted", (long long)rec.runaway);
+    if (rec.cancelled) return fail(KP_E_CANCELED, "%s simulations cancelled (kp_cancel_set)", what);
+    return KP_OK;
+  }
+};
+
+// kp_cluster_drift: every Solve runs whole; a launch leaves AllNonPendingPodsScheduled per subset in the verdict array
+// and, in its record, its lowest feasible subset, whose NodeClaims it finalizes; the host fetches that result when it
+// lowers the call's first
+struct DriftMode final : RecordMode {
+  Verdicts<DriftOut> v;
+  int64_t first = -1;                    // the lowest feasible caller-order subset so far
+  std::unique_ptr<kp_solve_result> res;  // its Solve result
+  DriftMode(kp_cluster_plan* p, GenTotals& t, kp_cancel* c, uint32_t n_subsets) : RecordMode(p, t, c, 0, "drift"), v(n_subsets) {}
+  int32_t Enqueue(const GenRun& R, GenSlot& sl) override {
+    // the verdicts, the launch's record, then every NodeClaim of its first feasible simulation finalized while the
+    // arena is resident (at most as many as the launch's longest queue, its first simulation's)
+    da.out = v.dev;
+    HIPCHK(launch_drift_verdict(da, sl.ks));
+    HIPCHK(launch_drift_first(da, sl.ks));
+    HIPCHK(launch_finalize_drift(sl.dfargs, da.rec, std::max(1, std::min(R.Pc, (int)R.len[R.order[sl.b0]])), sl.ks));
+    return KP_OK;
+  }
+  int32_t Decide(const GenRun& R, GenSlot& sl) override {
+    if (int32_t rc = RecordMode::Decide(R, sl)) return rc;
+    const DriftRec& rec = Record(sl);
+    if (rec.first >= 0 && (first < 0 || rec.first < first)) {
+      if (rec.local < 0 || rec.local >= sl.n || R.order[sl.b0 + (size_t)rec.local] != rec.first)
+        return fail(KP_E_DEVICE, "drift record: simulation %lld of the launch is not subset %lld", (long long)rec.local,
+                    (long long)rec.first);
+      if (int32_t rc = ArenaSolveResult(plan, R.gb, sl, (int)rec.local, R.cands[rec.first], res)) return rc;
+      first = rec.first;
+    }
+    return KP_OK;
+  }
+  // the verdict from the subset's own Solve (queue order: the Solve's own)
+  int32_t SimOne(const vector<uint32_t>& cand, int s) override {
+    SimOneSolve so;
+    if (int32_t rc = GeneralSolveOne(plan, cand, so, T, cancel)) return rc;
+    const kp_solve_result* r = so.res.get();
+    DriftOut o;
+    memset(&o, 0, sizeof o);
+    o.n_nodeclaims = (uint32_t)r->ncs.size();
+    o.n_pods = (uint32_t)so.kind.size();
+    o.first_unscheduled = -1;
+    for (int32_t p : so.sp->cp->queue)
+      if (PodUnscheduled(so.kind[p], r->placement[p], [&](int pos) { return so.ex[(size_t)pos].initialized != 0; }))
+        if (o.n_unscheduled++ == 0) o.first_unscheduled = (int32_t)so.cluster_pod[p];
+    o.feasible = o.n_unscheduled == 0 ? 1 : 0;
+    v.OnHost(s) = o;
+    if (o.feasible && (first < 0 || s < first)) {
+      first = s;
+      res.reset(so.res.release());
+    }
+    return KP_OK;
+  }
+};
+
+// kp_cluster_validate: the Solves stop at the second NodeClaim and are finalized as the consolidation launches are,
+// then validate_verdict_kernel (and validate_sum_kernel) leave the verdicts and the launch's record
+struct ValidateMode final : RecordMode {
+  const kp_command_check* checks;
+  vector<vector<string>> names;  // per subset: the check's names as a set (CheckNames)
+  Verdicts<ValOut> v;
+  const uint64_t* d_want = nullptr;  // the compiled checks on the device (ValidateCompile)
   const uint32_t* d_unknown = nullptr;
   const uint8_t* d_replace = nullptr;
+  ValidateMode(kp_cluster_plan* p, GenTotals& t, kp_cancel* c, const kp_command_check* ch, uint32_t n_subsets)
+      : RecordMode(p, t, c, 2, "validation"), checks(ch), names(n_subsets), v(n_subsets) {}
+  int32_t Enqueue(const GenRun& R, GenSlot& sl) override {
+    const GeneralBatch& gb = R.gb;
+    const SolveOffs& o = gb.o;
+    const SolveArgs& a0 = R.sargs[0];
+    HIPCHK(launch_finalize_batch(R.fargs[0], sl.dfargs, sl.n, sl.ks));
+    ValidateArgs va;
+    memset(&va, 0, sizeof va);
+    va.d = da;
+    va.off_nct = o.nct, va.off_nopt = o.nopt, va.off_opts = o.opts, va.off_ncr = o.ncr;
+    va.opt_stride = gb.opt_stride;
+    va.n_tmpl = (int32_t)gb.C->B->tmpl_catalog.size();
+    va.n_catalogs = (int32_t)gb.C->B->cats.size();
+    va.dict = a0.dict;
+    va.cats = a0.cats;
+    va.tmpl_catalog = a0.tmpl_catalog;
+    va.want = d_want;
+    va.unknown = d_unknown;
+    va.replace = d_replace;
+    va.out = v.dev;
+    HIPCHK(launch_validate_verdict(va, sl.ks));
+    return KP_OK;
+  }
+  // The rule applied on the host to the subset's own whole Solve (GeneralSolveOne). kp_solve_run has applied the held
+  // reservations and Truncate's minValues check to the NodeClaim (HostMinValuesOK: options cleared, pods unplaced).
+  int32_t SimOne(const vector<uint32_t>& cand, int s) override {
+    SimOneSolve so;
+    if (int32_t rc = GeneralSolveOne(plan, cand, so, T, cancel)) return rc;
+    const kp_cluster& cl = plan->cluster()->cl;
+    const kp_solve_result* res = so.res.get();
+    const bool repl = checks[s].decision == KP_DECISION_REPLACE;
+    ValOut& o = v.OnHost(s);
+    memset(&o, 0, sizeof o);
+    o.n_pods = (uint32_t)so.kind.size();
+    if (res->ncs.size() > 1) {
+      o.verdict = KP_INVALID_MULTIPLE;
+      o.n_nodeclaims = 2;
+      return KP_OK;
+    }
+    o.n_nodeclaims = (uint32_t)res->ncs.size();
+    for (size_t p = 0; p < so.kind.size(); p++)
+      if (PodUnscheduled(so.kind[p], res->placement[p], [&](int pos) { return so.ex[(size_t)pos].initialized != 0; }))
+        o.n_unscheduled++;
+    if (o.n_unscheduled) {
+      o.verdict = KP_INVALID_UNSCHEDULED;
+    } else if (res->ncs.empty()) {
+      o.verdict = repl ? KP_INVALID_NO_REPLACEMENT_NEEDED : KP_VALID;
+    } else if (!repl) {
+      o.verdict = KP_INVALID_NEEDS_REPLACEMENT;
+    } else {
+      const vector<HostType>& types = cl.catalogs[res->nc_cat[0]]->types;
+      std::set<string> have;
+      for (uint32_t t : res->ncs[0].options)
+        if (t < types.size()) have.insert(types[t].name);
+      for (const string& nm : names[s])
+        if (!have.count(nm)) o.n_missing++;
+      o.verdict = o.n_missing ? KP_INVALID_NOT_SUBSET : KP_VALID;
+    }
+    return KP_OK;
+  }
 };
-static int32_t ValidateSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand, int s, ValRun& vl, uint64_t* counters,
-                              double* dev_ms, kp_cancel* cancel);
-static int32_t DriftFetch(kp_cluster_plan* plan, GeneralBatch& gb, const GenSlot& sl, int j, const vector<uint32_t>& cand,
-                          std::unique_ptr<kp_solve_result>& out);
 
-// Runs the batchable subsets `idx` (their candidate lists in cands) as batched Solves; outs[idx[i]] get the decisions.
-// dr (kp_cluster_drift): the Solves run whole (no early stop), and instead of the decisions the launch leaves its
-// verdicts in dr->d_out and one record; the host reads the record and, when it lowers dr->first, the winner's result.
-static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const vector<vector<uint32_t>>& cands,
-                               const vector<int>& idx, const vector<std::map<string, string>>& labels, int32_t multi_node,
-                               vector<SimOut>& outs, uint64_t* counters, double* dev_ms, double* host_ms,
-                               kp_cancel* cancel, uint64_t* n_launches, DriftRun* dr = nullptr,
-                               kp_solve_result** commands = nullptr, ValRun* vl = nullptr) {
+// Runs the batchable subsets `idx` (their candidate lists in cands) as batched Solves, pipelined over the plan's two
+// launch slots; what the launches leave behind is the mode's.
+static int32_t GeneralBatchRun(GeneralBatch& gb, const vector<vector<uint32_t>>& cands, const vector<int>& idx,
+                               GeneralMode& mode) {
+  kp_cluster_plan* plan = mode.plan;
+  GenTotals& T = mode.T;
+  kp_cancel* cancel = mode.cancel;
   kp_ctx* ctx = plan->ctx;
   const kp_cluster& cl = plan->cluster()->cl;
   const Compiled& C = *gb.C;
@@ -6212,16 +6692,16 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
     ~Drain() { (void)hipStreamSynchronize(s); }
   } drain{st};
   // the arena size: every simulation of the batch fits (rounded up, so that nearby batches share a layout)
+  GenRun R{gb, cands, idx, vector<size_t>(cands.size(), 0)};
   size_t max_pods = 1;
-  vector<size_t> len(cands.size(), 0);
   for (int i : idx) {
     size_t n = gb.base_pods.size();
     for (uint32_t c : cands[i]) n += gb.node_pods[c].size();
-    len[i] = n;
+    R.len[i] = n;
     max_pods = std::max(max_pods, n);
   }
-  int Pc = 64;
-  while ((size_t)Pc < max_pods) Pc *= 2;
+  while ((size_t)R.Pc < max_pods) R.Pc *= 2;
+  const int Pc = R.Pc;
   if (int32_t rc = GeneralBatchLayout(ctx, gb, Pc)) return rc;
   const SolveOffs& o = gb.o;
   const size_t patch_bytes = o.common;
@@ -6236,10 +6716,11 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
   if (idx.size() > per_launch && idx.size() < 2 * per_launch) per_launch = (idx.size() + 1) / 2;  // two even launches
   // kp_overrides.general_launch (read now, not when the plan was prepared): small batches reach the reused arenas
   if (ctx->ov.general_launch > 0) per_launch = std::min<size_t>(per_launch, (size_t)ctx->ov.general_launch);
+  R.per_launch = per_launch;
   // longest simulations first (queue length: pending + the candidates' pods): they start on the first CUs instead
   // of trailing the launch
-  vector<int> order(idx);
-  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return len[x] > len[y]; });
+  const vector<int>& order = R.order;
+  std::stable_sort(R.order.begin(), R.order.end(), [&](int x, int y) { return R.len[x] > R.len[y]; });
   if (ctx->ov.host_timing)
     fprintf(stderr, "[kp general] arena stride %.2f MB, %zu simulations per launch, Pc %d; batch_init per simulation: copy %zu B, "
             "fills stats %zu npods %zu place %zu ver %zu fail %zu hcnc %zu B\n", gb.stride / 1e6, per_launch, Pc,
@@ -6249,166 +6730,34 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
   const int sort_cap = std::min(SortCapacity(C.ov), Pc);
   const size_t dyn = std::max<size_t>((size_t)2 * sort_cap * sizeof(int32_t), o.chk_on ? CHK_LDS_BYTES : 0);
   vector<GenScratch> scratches(kMaxHostThreads);
-  vector<SolveArgs> sargs;
-  vector<FinalizeArgs> fargs;
-  // per-launch result layout in the slot's pinned download buffer
-  const size_t r_stats = 0, r_place = r_stats + sizeof(uint64_t) * KP_SOLVE_STATS * per_launch;
-  const size_t r_nct = r_place + sizeof(int32_t) * (size_t)Pc * per_launch;
-  const size_t r_nopt = r_nct + sizeof(int32_t) * per_launch;
-  const size_t r_opts = r_nopt + sizeof(uint32_t) * per_launch;
-  const size_t r_fin = (r_opts + sizeof(uint32_t) * (size_t)gb.opt_stride * per_launch + 63) & ~(size_t)63;
-  const size_t r_held = r_fin + sizeof(KReqs) * per_launch;
-  const size_t r_end = r_held + sizeof(uint64_t) * per_launch;
-  const size_t u_args = (patch_bytes * per_launch + 255) & ~(size_t)255;
-  const size_t u_fargs = u_args + ((sizeof(SolveArgs) * per_launch + 255) & ~(size_t)255);
-  const size_t u_end = u_fargs + sizeof(FinalizeArgs) * per_launch;
-  // drift launches: the slot's drift buffer (queue pods [n][Pc], lengths [n], caller indices [n], then the record),
-  // mirrored in the upload buffer behind the arguments
-  const size_t d_qlen = sizeof(int32_t) * (size_t)Pc * per_launch, d_cidx = d_qlen + sizeof(int32_t) * per_launch;
-  const size_t d_rec = (d_cidx + sizeof(int32_t) * per_launch + 255) & ~(size_t)255;
-  const size_t u_drift = (u_end + 255) & ~(size_t)255;
-  // (validation launches, vl: the same buffers; their Solves stop at the second NodeClaim and are finalized as the
-  // consolidation launches are, then validate_verdict_kernel and validate_sum_kernel leave the verdicts and one record)
-  const bool rec_mode = dr || vl;
-  const size_t up_need = rec_mode ? u_drift + d_rec : u_end, down_need = rec_mode ? sizeof(DriftRec) : r_end;
+  vector<SolveArgs>& sargs = R.sargs;
+  vector<FinalizeArgs>& fargs = R.fargs;
+  R.r_place = R.r_stats + sizeof(uint64_t) * KP_SOLVE_STATS * per_launch;
+  R.r_nct = R.r_place + sizeof(int32_t) * (size_t)Pc * per_launch;
+  R.r_nopt = R.r_nct + sizeof(int32_t) * per_launch;
+  R.r_opts = R.r_nopt + sizeof(uint32_t) * per_launch;
+  R.r_fin = (R.r_opts + sizeof(uint32_t) * (size_t)gb.opt_stride * per_launch + 63) & ~(size_t)63;
+  R.r_held = R.r_fin + sizeof(KReqs) * per_launch;
+  R.r_end = R.r_held + sizeof(uint64_t) * per_launch;
+  R.u_args = (patch_bytes * per_launch + 255) & ~(size_t)255;
+  R.u_fargs = R.u_args + ((sizeof(SolveArgs) * per_launch + 255) & ~(size_t)255);
+  R.u_end = R.u_fargs + sizeof(FinalizeArgs) * per_launch;
+  R.u_rec = (R.u_end + 255) & ~(size_t)255;
+  R.d_qlen = sizeof(int32_t) * (size_t)Pc * per_launch;
+  R.d_cidx = R.d_qlen + sizeof(int32_t) * per_launch;
+  R.d_rec = (R.d_cidx + sizeof(int32_t) * per_launch + 255) & ~(size_t)255;
 
-  // the host decisions of a finished launch (its results in the slot's download buffer)
+  // a finished launch: its results have landed; its kernels' time; then the mode's decisions
   auto decide = [&](GenSlot& sl) -> int32_t {
     HIPCHK(hipEventSynchronize(sl.done));
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, sl.t0, sl.t1));
-    *dev_ms += ms;
+    T.dev_ms += ms;
     const auto th1 = std::chrono::steady_clock::now();
-    const int n = sl.n;
-    const size_t b0 = sl.b0;
-    const uint64_t* stats = reinterpret_cast<uint64_t*>(sl.down.at(r_stats));
-    const int32_t* place = reinterpret_cast<int32_t*>(sl.down.at(r_place));
-    const int32_t* nct = reinterpret_cast<int32_t*>(sl.down.at(r_nct));
-    const uint32_t* nopt = reinterpret_cast<uint32_t*>(sl.down.at(r_nopt));
-    uint32_t* opts = reinterpret_cast<uint32_t*>(sl.down.at(r_opts));
-    const KReqs* fin = reinterpret_cast<KReqs*>(sl.down.at(r_fin));
-    const uint64_t* held = reinterpret_cast<uint64_t*>(sl.down.at(r_held));
-    const vector<vector<int32_t>>& queues = sl.queues;
-    std::atomic<int> bad_runaway{-1}, cancelled{0};
-    uint64_t tcount[kMaxHostThreads][3] = {}, tphase[kMaxHostThreads][8] = {};
-    // kp_cluster_command: the options each decision kept and whether it was taken as spot-to-spot
-    vector<vector<int>> keptv(commands ? n : 0);
-    vector<uint8_t> s2sv(commands ? n : 0, 0);
-    ParallelFor(n, [&](int j_lo, int j_hi, int t) {
-    for (int j = j_lo; j < j_hi; j++) {
-      const int i = order[b0 + j];
-      const uint64_t* sj = &stats[(size_t)j * KP_SOLVE_STATS];
-      if (sj[7]) {
-        bad_runaway = i;
-        return;
-      }
-      if (sj[46]) {
-        cancelled = 1;
-        return;
-      }
-      tcount[t][0] += sj[0];
-      tcount[t][1] += sj[1];
-      tcount[t][2] += sj[2];
-      for (int k = 0; k < 8; k++) tphase[t][k] += sj[8 + k];  // (zero unless kp_overrides.timing)
-      const int n_nc = (int)sj[3];
-      const vector<int32_t>& q = queues[j];
-      SimOut& r = outs[i];
-      r.n_pods = (uint32_t)q.size();
-      // AllNonPendingPodsScheduled; a candidate pod on an uninitialized node is an error (deleting-node pods exempt)
-      bool all = true;
-      for (size_t p = 0; p < q.size() && all; p++) {
-        const uint8_t kind = gb.pod_kind[q[p]];
-        const int32_t pl = place[(size_t)j * Pc + p];
-        if (kind == 2) continue;
-        if (pl == -1) all = false;
-        else if (kind == 0 && pl <= -2 && !cl.nodes[gb.pos_node[-2 - pl]].node.initialized) all = false;
-      }
-      KReqs R = fin[j];
-      int ci = 0;
-      uint32_t np = 0;
-      if (n_nc == 1) {
-        if (gb.res_mode) ApplyHeld(*C.B, held[j], R);
-        ci = C.B->tmpl_catalog[nct[j]];
-        np = (uint32_t)C.B->tmpl_nodepool[nct[j]];
-      }
-      bool s2s = false;
-      GeneralDecide(cl, labels, cands[i], *C.B, all, n_nc, &R, ci, np, &opts[(size_t)j * gb.opt_stride],
-                    n_nc == 1 ? nopt[j] : 0, multi_node, r, &gb.offers, &gb.cands, commands ? &keptv[j] : nullptr, &s2s);
-      if (commands) s2sv[j] = s2s ? 1 : 0;
-    }
-    });
-    for (int t = 0; t < kMaxHostThreads; t++) {
-      for (int k = 0; k < 3; k++) counters[k] += tcount[t][k];
-      for (int k = 0; k < 8; k++) plan->general_phase[k] += tphase[t][k];
-    }
-    if (bad_runaway >= 0)
-      return fail(KP_E_DEVICE, "solve_kernel exceeded its Queue.Pop bound in simulation %d: aborted", bad_runaway.load());
-    if (cancelled) return fail(KP_E_CANCELED, "consolidation simulations cancelled (kp_cancel_set)");
-    // kp_cluster_command: the command of every simulation that decided DELETE or REPLACE, from its arena while the
-    // slot still holds it (the launch after the next overwrites it, and is not queued yet), as drift mode reads its
-    // winner: FetchArenaResult + AssembleResult, then the NodeClaim's options cut to the ones the decision kept. A
-    // simulation that stopped at its second NodeClaim decided no-op and is not read.
-    for (int j = 0; commands && j < n; j++) {
-      const int i = order[b0 + j];
-      if (outs[i].decision == KP_DECISION_NOOP) continue;
-      std::unique_ptr<kp_solve_result> res;
-      if (int32_t rc = DriftFetch(plan, gb, sl, j, cands[i], res)) return rc;
-      const bool replace = outs[i].decision == KP_DECISION_REPLACE;
-      if (res->ncs.size() != (replace ? 1u : 0u))
-        return fail(KP_E_DEVICE, "command of subset %d: %zu NodeClaims in its arena", i, res->ncs.size());
-      if (replace) {
-        res->ncs[0].options.assign(keptv[j].begin(), keptv[j].end());
-        if (s2sv[j]) {
-          NarrowToSpot(C.B->d, res->fin[0]);
-          res->ncs[0].reqs = DecodeReqs(C.B->d, res->fin[0]);
-        }
-      }
-      commands[i] = res.release();
-    }
-    host_ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th1).count();
+    if (int32_t rc = mode.Decide(R, sl)) return rc;
+    T.host_ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th1).count();
     return KP_OK;
   };
-
-  // drift: the launch's record; its first feasible simulation's result when that lowers the call's first
-  auto decide_drift = [&](GenSlot& sl) -> int32_t {
-    HIPCHK(hipEventSynchronize(sl.done));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, sl.t0, sl.t1));
-    *dev_ms += ms;
-    const auto th1 = std::chrono::steady_clock::now();
-    const DriftRec rec = *reinterpret_cast<const DriftRec*>(sl.down.at(0));
-    counters[0] += rec.attempts;
-    counters[1] += rec.bytes;
-    counters[2] += rec.pops;
-    if (rec.runaway >= 0)
-      return fail(KP_E_DEVICE, "solve_kernel exceeded its Queue.Pop bound in simulation %lld: aborted", (long long)rec.runaway);
-    if (rec.cancelled) return fail(KP_E_CANCELED, "drift simulations cancelled (kp_cancel_set)");
-    if (rec.first >= 0 && (dr->first < 0 || rec.first < dr->first)) {
-      if (rec.local < 0 || rec.local >= sl.n || order[sl.b0 + (size_t)rec.local] != rec.first)
-        return fail(KP_E_DEVICE, "drift record: simulation %lld of the launch is not subset %lld", (long long)rec.local,
-                    (long long)rec.first);
-      if (int32_t rc = DriftFetch(plan, gb, sl, (int)rec.local, cands[rec.first], dr->res)) return rc;
-      dr->first = rec.first;
-    }
-    host_ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th1).count();
-    return KP_OK;
-  };
-  // validation: the launch's record (counters, a runaway Solve, cancellation)
-  auto decide_val = [&](GenSlot& sl) -> int32_t {
-    HIPCHK(hipEventSynchronize(sl.done));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, sl.t0, sl.t1));
-    *dev_ms += ms;
-    const DriftRec rec = *reinterpret_cast<const DriftRec*>(sl.down.at(0));
-    counters[0] += rec.attempts;
-    counters[1] += rec.bytes;
-    counters[2] += rec.pops;
-    if (rec.runaway >= 0)
-      return fail(KP_E_DEVICE, "solve_kernel exceeded its Queue.Pop bound in simulation %lld: aborted", (long long)rec.runaway);
-    if (rec.cancelled) return fail(KP_E_CANCELED, "validation simulations cancelled (kp_cancel_set)");
-    return KP_OK;
-  };
-  auto decide_any = [&](GenSlot& sl) -> int32_t { return vl ? decide_val(sl) : dr ? decide_drift(sl) : decide(sl); };
 
   GenSlot* slots = gb.slot;
   for (int k = 0; k < 2; k++)
@@ -6418,13 +6767,11 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
       HIPCHK(hipEventCreate(&slots[k].t0));
       HIPCHK(hipEventCreate(&slots[k].t1));
     }
-  if (!gb.cs.up) {
-    HIPCHK(hipStreamCreateWithFlags(&gb.cs.up, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&gb.cs.down, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&gb.cs.k[0], hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&gb.cs.k[1], hipStreamNonBlocking));
-  }
-  hipStream_t up = gb.cs.up, dn = gb.cs.down;
+  if (!gb.cs.up)
+    for (hipStream_t* x : {&gb.cs.up, &gb.cs.down, &gb.cs.k[0], &gb.cs.k[1]})
+      HIPCHK(hipStreamCreateWithFlags(x, hipStreamNonBlocking));
+  hipStream_t up = R.up = gb.cs.up, dn = R.dn = gb.cs.down;
+  slots[0].ks = gb.cs.k[0], slots[1].ks = gb.cs.k[1];
   struct DrainCopies {  // (early returns: nothing left in flight on the copy or kernel streams either)
     hipStream_t u, d, k0, k1;
     ~DrainCopies() {
@@ -6440,7 +6787,7 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
     const auto th0 = std::chrono::steady_clock::now();
     const int n = (int)std::min(per_launch, idx.size() - b0);
     // arenas for this launch's n simulations, grown geometrically (a few subsets do not pin gigabytes on the plan);
-    // when the device cannot hold them, this batch and the rest run one simulation at a time (GeneralSimOne)
+    // when the device cannot hold them, this batch and the rest run one simulation at a time (the mode's SimOne)
     hipError_t ae = hipSuccess;
     if (sl.arenas_bytes < gb.stride * n) {
       const size_t sims = std::min(per_launch, std::max<size_t>((size_t)n, 2 * sl.arenas_bytes / gb.stride));
@@ -6452,26 +6799,20 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
       ae = sl.args.alloc(args_need);
       sl.args_bytes = ae == hipSuccess ? args_need : 0;
     }
-    if (ae == hipSuccess) ae = sl.up.reserve(up_need);
-    if (ae == hipSuccess) ae = sl.down.reserve(down_need);
-    if (ae == hipSuccess && rec_mode && sl.drift_bytes < d_rec + sizeof(DriftRec)) {
-      ae = sl.drift.alloc(d_rec + sizeof(DriftRec));
-      sl.drift_bytes = ae == hipSuccess ? d_rec + sizeof(DriftRec) : 0;
-    }
+    if (ae == hipSuccess) ae = mode.Reserve(R, sl);
     if (ae != hipSuccess) {
       (void)hipGetLastError();
       if (pending >= 0) {
-        if (int32_t rc = decide_any(slots[pending])) return rc;
+        if (int32_t rc = decide(slots[pending])) return rc;
         pending = -1;
       }
       for (size_t j = b0; j < idx.size(); j++)
-        if (int32_t rc = vl ? ValidateSimOne(plan, cands[order[j]], order[j], *vl, counters, dev_ms, cancel)
-                         : dr ? DriftSimOne(plan, cands[order[j]], order[j], *dr, counters, dev_ms, cancel)
-                            : GeneralSimOne(plan, cands[order[j]], labels, multi_node, outs[order[j]], counters, dev_ms, cancel,
-                                            commands ? &commands[order[j]] : nullptr))
-          return rc;
+        if (int32_t rc = mode.SimOne(cands[order[j]], order[j])) return rc;
       break;
     }
+    // (this slot's previous launch was decided before the launch in flight was queued)
+    sl.n = n;
+    sl.b0 = b0;
     uint8_t* arenas = (uint8_t*)sl.arenas.p;
     uint8_t* sh = (uint8_t*)gb.shared.p;
     uint8_t* patches = reinterpret_cast<uint8_t*>(sl.up.at(0));
@@ -6495,9 +6836,7 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
       SolveArgs& a = sargs[j];
       BindSolve(a, C, o, sh, ar, (int)queues[j].size(), Pc, gb.rmask, gb.res_mode);
       a.cancel = dcancel;
-      // a second NodeClaim decides a consolidation simulation (no-op): the kernel ends its Solve there; a drift
-      // simulation is the whole Solve
-      a.stop_nc = dr ? 0 : 2;
+      a.stop_nc = mode.stop_nc;
       a.ex_reqs_ro = (const uint8_t*)gb.pristine.p + (o.exr - o.common);  // (the arena's copy is written on demand)
       a.ex_ulist = (const int32_t*)(sh + gb.so.exul);
       a.ex_ulist_off = (const int32_t*)(sh + gb.so.exuo);
@@ -6532,10 +6871,11 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
               launch_no, n, patch_bytes, tp,
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th0).count());
     }
-    memcpy(reinterpret_cast<uint8_t*>(sl.up.at(u_args)), sargs.data(), sizeof(SolveArgs) * n);
-    memcpy(reinterpret_cast<uint8_t*>(sl.up.at(u_fargs)), fargs.data(), sizeof(FinalizeArgs) * n);
+    memcpy(reinterpret_cast<uint8_t*>(sl.up.at(R.u_args)), sargs.data(), sizeof(SolveArgs) * n);
+    memcpy(reinterpret_cast<uint8_t*>(sl.up.at(R.u_fargs)), fargs.data(), sizeof(FinalizeArgs) * n);
     SolveArgs* dargs = (SolveArgs*)sl.args.p;
     FinalizeArgs* dfargs = (FinalizeArgs*)((uint8_t*)sl.args.p + ((sizeof(SolveArgs) * n + 255) & ~(size_t)255));
+    sl.dfargs = dfargs;
     BatchInitArgs bi;
     memset(&bi, 0, sizeof bi);
     bi.base = arenas;
@@ -6561,107 +6901,34 @@ static int32_t GeneralBatchRun(kp_cluster_plan* plan, GeneralBatch& gb, const ve
     fill(o.ver0, o.ver_end - o.ver0, 0);
     fill(o.fail0, o.fail_end - o.fail0, 0xFF);
     if (o.n_hcnc) fill(o.hcnc, o.n_hcnc, 0);
-    host_ms[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th0).count();
+    T.host_ms[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th0).count();
     // uploads on their own stream (they overlap the previous launch's kernels; this slot's arenas and buffers were
     // last used by the launch before that one, whose results decide() has already waited for); batch_init writes
     // [common, mut_end) of the arenas, the overlays [0, common)
     HIPCHK(hipMemcpy2DAsync(arenas, gb.stride, patches, patch_bytes, patch_bytes, n, hipMemcpyHostToDevice, up));
-    HIPCHK(hipMemcpyAsync(dargs, reinterpret_cast<uint8_t*>(sl.up.at(u_args)), sizeof(SolveArgs) * n, hipMemcpyHostToDevice, up));
-    HIPCHK(hipMemcpyAsync(dfargs, reinterpret_cast<uint8_t*>(sl.up.at(u_fargs)), sizeof(FinalizeArgs) * n, hipMemcpyHostToDevice, up));
-    DriftArgs da;
-    memset(&da, 0, sizeof da);
-    if (rec_mode) {
-      uint8_t* hd = sl.up.at(u_drift);
-      uint8_t* dd = (uint8_t*)sl.drift.p;
-      int32_t* qpod = reinterpret_cast<int32_t*>(hd);
-      int32_t* qlen = reinterpret_cast<int32_t*>(hd + d_qlen);
-      int32_t* cidx = reinterpret_cast<int32_t*>(hd + d_cidx);
-      for (int j = 0; j < n; j++) {
-        memcpy(qpod + (size_t)j * Pc, queues[j].data(), sizeof(int32_t) * queues[j].size());
-        qlen[j] = (int32_t)queues[j].size();
-        cidx[j] = order[b0 + j];
-      }
-      HIPCHK(hipMemcpyAsync(dd, hd, sizeof(int32_t) * (size_t)Pc * n, hipMemcpyHostToDevice, up));
-      HIPCHK(hipMemcpyAsync(dd + d_qlen, hd + d_qlen, sizeof(int32_t) * n, hipMemcpyHostToDevice, up));
-      HIPCHK(hipMemcpyAsync(dd + d_cidx, hd + d_cidx, sizeof(int32_t) * n, hipMemcpyHostToDevice, up));
-      da.n = n;
-      da.Pc = Pc;
-      da.n_existing = (int32_t)C.ex_input.size();
-      da.n_super = (int32_t)gb.pod_kind.size();
-      da.arenas = arenas;
-      da.stride = gb.stride;
-      da.off_place = o.place;
-      da.off_stats = o.stats;
-      da.qpod = reinterpret_cast<const int32_t*>(dd);
-      da.qlen = reinterpret_cast<const int32_t*>(dd + d_qlen);
-      da.cidx = reinterpret_cast<const int32_t*>(dd + d_cidx);
-      da.pod_kind = gb.d_pod_kind;
-      da.pod_cluster = gb.d_pod_cluster;
-      da.pos_uninit = gb.d_pos_uninit;
-      da.out = dr ? dr->d_out : nullptr;
-      da.rec = reinterpret_cast<DriftRec*>(dd + d_rec);
-    }
+    HIPCHK(hipMemcpyAsync(dargs, reinterpret_cast<uint8_t*>(sl.up.at(R.u_args)), sizeof(SolveArgs) * n, hipMemcpyHostToDevice, up));
+    HIPCHK(hipMemcpyAsync(dfargs, reinterpret_cast<uint8_t*>(sl.up.at(R.u_fargs)), sizeof(FinalizeArgs) * n, hipMemcpyHostToDevice, up));
+    if (int32_t rc = mode.Upload(R, sl)) return rc;
     HIPCHK(hipEventRecord(sl.uploaded, up));
-    hipStream_t ks = gb.cs.k[launch_no & 1];  // (the slot's kernel stream)
-    HIPCHK(launch_batch_init(bi, n, ks));
-    HIPCHK(hipStreamWaitEvent(ks, sl.uploaded, 0));
-    HIPCHK(hipEventRecord(sl.t0, ks));
-    HIPCHK(launch_solve_batch(sargs[0], dargs, n, dyn, ks));
-    if (dr) {
-      // the verdicts, the launch's record, then every NodeClaim of its first feasible simulation finalized while the
-      // arena is resident (at most as many as the launch's longest queue, its first simulation's)
-      HIPCHK(launch_drift_verdict(da, ks));
-      HIPCHK(launch_drift_first(da, ks));
-      HIPCHK(launch_finalize_drift(dfargs, da.rec, std::max(1, std::min(Pc, (int)len[order[b0]])), ks));
-    } else {
-      HIPCHK(launch_finalize_batch(fargs[0], dfargs, n, ks));
-    }
-    if (vl) {
-      ValidateArgs va;
-      memset(&va, 0, sizeof va);
-      va.d = da;
-      va.off_nct = o.nct, va.off_nopt = o.nopt, va.off_opts = o.opts, va.off_ncr = o.ncr;
-      va.opt_stride = gb.opt_stride;
-      va.n_tmpl = (int32_t)C.B->tmpl_catalog.size();
-      va.n_catalogs = (int32_t)C.B->cats.size();
-      va.dict = sargs[0].dict;
-      va.cats = sargs[0].cats;
-      va.tmpl_catalog = sargs[0].tmpl_catalog;
-      va.want = vl->d_want;
-      va.unknown = vl->d_unknown;
-      va.replace = vl->d_replace;
-      va.out = vl->d_out;
-      HIPCHK(launch_validate_verdict(va, ks));
-    }
-    HIPCHK(hipEventRecord(sl.t1, ks));
+    HIPCHK(launch_batch_init(bi, n, sl.ks));
+    HIPCHK(hipStreamWaitEvent(sl.ks, sl.uploaded, 0));
+    HIPCHK(hipEventRecord(sl.t0, sl.ks));
+    HIPCHK(launch_solve_batch(sargs[0], dargs, n, dyn, sl.ks));
+    if (int32_t rc = mode.Enqueue(R, sl)) return rc;
+    HIPCHK(hipEventRecord(sl.t1, sl.ks));
     // downloads on their own stream once the kernels are done (the next launch's kernels need not wait for them)
     HIPCHK(hipStreamWaitEvent(dn, sl.t1, 0));
-    if (rec_mode) {  // drift and validation launches download the record only (the verdicts: one copy at the end of the call)
-      HIPCHK(hipMemcpyAsync(sl.down.at(0), da.rec, sizeof(DriftRec), hipMemcpyDeviceToHost, dn));
-    } else {
-      auto down = [&](size_t roff, size_t off, size_t width) {
-        return hipMemcpy2DAsync(reinterpret_cast<uint8_t*>(sl.down.at(roff)), width, arenas + off, gb.stride, width, n, hipMemcpyDeviceToHost, dn);
-      };
-      HIPCHK(down(r_stats, o.stats, sizeof(uint64_t) * KP_SOLVE_STATS));
-      HIPCHK(down(r_place, o.place, sizeof(int32_t) * Pc));
-      HIPCHK(down(r_nct, o.nct, sizeof(int32_t)));
-      HIPCHK(down(r_nopt, o.nopt, sizeof(uint32_t)));
-      HIPCHK(down(r_opts, o.opts, sizeof(uint32_t) * gb.opt_stride));
-      HIPCHK(down(r_fin, o.ncr, sizeof(KReqs)));
-      if (gb.res_mode) HIPCHK(down(r_held, o.held, sizeof(uint64_t)));
-    }
+    if (int32_t rc = mode.Download(R, sl)) return rc;
     HIPCHK(hipEventRecord(sl.done, dn));
-    sl.n = n;
-    sl.b0 = b0;
     // the previous launch's decisions while this one runs
     if (pending >= 0) {
-      if (int32_t rc = decide_any(slots[pending])) return rc;
+      if (int32_t rc = decide(slots[pending])) return rc;
     }
     pending = launch_no & 1;
-    ++*n_launches;
+    ++T.n_launches;
   }
   if (pending >= 0) {
-    if (int32_t rc = decide_any(slots[pending])) return rc;
+    if (int32_t rc = decide(slots[pending])) return rc;
   }
   return KP_OK;
 }
@@ -6798,22 +7065,17 @@ static int32_t GeneralSimLocked(kp_cluster_plan* plan, const uint32_t* offsets, 
   const double t_setup = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
   vector<SimOut> outs(n_subsets);
   memset(outs.data(), 0, sizeof(SimOut) * outs.size());
-  uint64_t counters[3] = {0, 0, 0}, n_launches = 0;
+  GenTotals T;
+  T.batched = batched.size(), T.single = single.size();
   memset(plan->general_phase, 0, sizeof plan->general_phase);
-  double dev_ms = 0, host_ms[2] = {0, 0};  // the batch's host work: overlays + arguments, decisions
+  ConsolidateMode mode(plan, T, cancel, labels, multi_node, outs, commands);
   const auto t1 = clk::now();
-  if (!batched.empty()) {
-    const int32_t rc = GeneralBatchRun(plan, *plan->gb, cands, batched, labels, multi_node, outs, counters, &dev_ms, host_ms,
-                                       cancel, &n_launches, nullptr, commands);
-    if (rc) return rc;
-  }
+  if (!batched.empty())
+    if (int32_t rc = GeneralBatchRun(*plan->gb, cands, batched, mode)) return rc;
   const double t_batch = std::chrono::duration<double, std::milli>(clk::now() - t1).count();
   const auto t2 = clk::now();
-  for (int s : single) {
-    const int32_t rc = GeneralSimOne(plan, cands[s], labels, multi_node, outs[s], counters, &dev_ms, cancel,
-                                     commands ? &commands[s] : nullptr);
-    if (rc) return rc;
-  }
+  for (int s : single)
+    if (int32_t rc = mode.SimOne(cands[s], s)) return rc;
   const double t_single = std::chrono::duration<double, std::milli>(clk::now() - t2).count();
   // results and counters in device buffers, as the batched kernel leaves them
   const size_t need = sizeof(SimOut) * std::max<uint32_t>(n_subsets, 1) + 256 + sizeof(uint64_t) * 8;
@@ -6826,129 +7088,24 @@ static int32_t GeneralSimLocked(kp_cluster_plan* plan, const uint32_t* offsets, 
   a = SimArgs{};
   a.out = (SimOut*)plan->batch.p;
   a.stats = (uint64_t*)((uint8_t*)plan->batch.p + ((sizeof(SimOut) * std::max<uint32_t>(n_subsets, 1) + 255) & ~(size_t)255));
-  uint64_t st[8] = {counters[0], counters[1], counters[2], (uint64_t)batched.size(), (uint64_t)single.size(), 0, n_launches,
-                    0};
+  uint64_t st[8] = {T.counters[0], T.counters[1], T.counters[2], T.batched, T.single, 0, T.n_launches, 0};
   if (n_subsets) HIPCHK(hipMemcpyAsync(a.out, outs.data(), sizeof(SimOut) * n_subsets, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(a.stats, st, sizeof st, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  plan->general_ms = dev_ms;
+  plan->general_ms = T.dev_ms;
   plan->general_batched = (uint32_t)batched.size();
   if (ctx->ov.host_timing)
     fprintf(stderr, "[kp general] %u sims (%zu batched, %zu single): setup %.2f batch %.2f (overlays %.2f decisions %.2f "
-            "device %.2f) single %.2f ms\n", n_subsets, batched.size(), single.size(), t_setup, t_batch, host_ms[0],
-            host_ms[1], dev_ms, t_single);
+            "device %.2f) single %.2f ms\n", n_subsets, batched.size(), single.size(), t_setup, t_batch, T.host_ms[0],
+            T.host_ms[1], T.dev_ms, t_single);
   return KP_OK;
 }
 
 // ---- Drift (kp_cluster_drift) ----------------------------------------------------------------------------------
 // Each subset is the simulation above run as a whole Solve; what comes back is AllNonPendingPodsScheduled per subset
-// and the Solve result of the first feasible one. Batched subsets: solve_kernel (stop_nc 0), drift_verdict_kernel,
-// drift_first_kernel and finalize_drift_kernel per launch (GeneralBatchRun); the others: their own Solve, the verdict
-// taken on the host from the result kp_solve_run has already copied back.
-
-// drift_verdict_kernel's gathers, uploaded once per superset Solve: pod kind and cluster pod per superset pod, the
-// "not initialized" byte per existing position
-static int32_t DriftTables(kp_ctx* ctx, GeneralBatch& gb, const kp_cluster& cl) {
-  if (gb.drift_tab.p) return KP_OK;
-  const size_t P = gb.pod_kind.size(), E = gb.pos_node.size();
-  const size_t o_cl = (P + 255) & ~(size_t)255, o_un = (o_cl + sizeof(int32_t) * P + 255) & ~(size_t)255;
-  vector<uint8_t> h(o_un + std::max<size_t>(E, 1), 0);
-  if (P) memcpy(h.data(), gb.pod_kind.data(), P);
-  if (P) memcpy(h.data() + o_cl, gb.pod_cluster.data(), sizeof(int32_t) * P);
-  for (size_t e = 0; e < E; e++) h[o_un + e] = cl.nodes[gb.pos_node[e]].node.initialized ? 0 : 1;
-  HIPCHK(gb.drift_tab.alloc(h.size()));
-  HIPCHK(hipMemcpyAsync(gb.drift_tab.p, h.data(), h.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  const uint8_t* d = (const uint8_t*)gb.drift_tab.p;
-  gb.d_pod_kind = d;
-  gb.d_pod_cluster = reinterpret_cast<const int32_t*>(d + o_cl);
-  gb.d_pos_uninit = d + o_un;
-  return KP_OK;
-}
-
-// The Solve result of simulation j of a finished drift launch, read from its arena (still resident: the slot is reused
-// by the launch after the next, which is not queued yet): what kp_solve_run copies back, in kp_cluster_drift's indices
-// (pods in the simulation's input order, existing nodes among those neither in the subset nor being deleted).
-static int32_t DriftFetch(kp_cluster_plan* plan, GeneralBatch& gb, const GenSlot& sl, int j, const vector<uint32_t>& cand,
-                          std::unique_ptr<kp_solve_result>& out) {
-  kp_ctx* ctx = plan->ctx;
-  const kp_cluster& cl = plan->cluster()->cl;
-  const Compiled& C = *gb.C;
-  const SolveOffs& o = gb.o;
-  const int Pc = gb.Pc, opt_stride = gb.opt_stride;
-  const uint8_t* ar = (const uint8_t*)sl.arenas.p + gb.stride * (size_t)j;
-  const vector<int32_t>& q = sl.queues[j];
-  hipStream_t st = ctx->stream;
-  uint64_t stats[KP_SOLVE_STATS];
-  HIPCHK(hipMemcpyAsync(stats, ar + o.stats, sizeof stats, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  const int P = (int)q.size();
-  if (P > Pc) return fail(KP_E_DEVICE, "drift result: %d pods in an arena of %d", P, Pc);
-  ArenaResult a;
-  const ResultOffs ro{o.place, o.events, o.nct, o.ncrq, o.opts, o.nrem, o.nopt, o.ncr, o.held};
-  if (int32_t rc = FetchArenaResult(st, ar, ro, Pc, opt_stride, gb.res_mode != 0, (int)stats[3], a)) return rc;
-  // queue position -> input index: the base pods are the superset's first pods in input order already; the subset's
-  // follow in subset order
-  const int n_base = (int)gb.base_pods.size(), N = (int)cl.n_nodes;
-  std::unordered_map<int32_t, int32_t> sub_in;
-  int32_t next = n_base;
-  for (uint32_t c : cand)
-    for (int32_t sp : gb.node_pods[c]) sub_in[sp] = next++;
-  vector<int32_t> in_of(P);
-  for (int p = 0; p < P; p++) in_of[p] = q[p] < n_base ? q[p] : sub_in.at(q[p]);
-  // existing position -> index among the nodes neither in the subset nor being deleted, cluster order
-  vector<int32_t> ex_rank(N, -1);
-  {
-    vector<char> inS(N, 0);
-    for (uint32_t c : cand) inS[c] = 1;
-    int32_t r = 0;
-    for (int i = 0; i < N; i++)
-      if (!inS[i] && !cl.nodes[i].deleting) ex_rank[i] = r++;
-  }
-  auto res = std::make_unique<kp_solve_result>();
-  if (int32_t rc = AssembleResult(*C.B, stats, a, P, opt_stride, [&](int p) { return in_of[p]; },
-                                  [&](int pos) { return pos < (int)gb.pos_node.size() ? ex_rank[gb.pos_node[pos]] : -1; }, *res))
-    return rc;
-  memset(&res->stats, 0, sizeof res->stats);
-  res->stats.attempts = stats[0];
-  res->stats.bytes_algorithmic = stats[1];
-  res->stats.pops = stats[2];
-  res->stats.scanned = stats[5];
-  res->stats.cursor_starts = stats[6];
-  res->stats.prepare_ms = plan->prepare_ms;
-  out = std::move(res);
-  return KP_OK;
-}
-
-// A subset compiled on its own: its Solve, the verdict from the result on the host (queue order: the Solve's own)
-static int32_t DriftSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand, int s, DriftRun& dr, uint64_t* counters,
-                           double* dev_ms, kp_cancel* cancel) {
-  SimOneSolve so;
-  if (int32_t rc = GeneralSolveOne(plan, cand, so, counters, dev_ms, cancel)) return rc;
-  const kp_solve_result* res = so.res.get();
-  DriftOut o;
-  memset(&o, 0, sizeof o);
-  o.n_nodeclaims = (uint32_t)res->ncs.size();
-  o.n_pods = (uint32_t)so.kind.size();
-  o.first_unscheduled = -1;
-  for (int32_t p : so.sp->cp->queue) {
-    const int32_t pl = res->placement[p];
-    const int kind = so.kind[p];
-    if (kind == 2) continue;
-    if (pl == -1 || (kind == 0 && pl <= -2 && !so.ex[(size_t)(-2 - pl)].initialized)) {
-      if (o.n_unscheduled++ == 0) o.first_unscheduled = (int32_t)so.cluster_pod[p];
-    }
-  }
-  o.feasible = o.n_unscheduled == 0 ? 1 : 0;
-  dr.host_out[s] = o;
-  dr.on_host[s] = 1;
-  if (o.feasible && (dr.first < 0 || s < dr.first)) {
-    dr.first = s;
-    dr.res.reset(so.res.release());
-  }
-  return KP_OK;
-}
-
+// and the Solve result of the first feasible one (DriftMode). Batched subsets: solve_kernel (stop_nc 0),
+// drift_verdict_kernel, drift_first_kernel and finalize_drift_kernel per launch; the others: their own Solve, the
+// verdict taken on the host from the result kp_solve_run has already copied back.
 static int32_t DriftLocked(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
                            uint32_t n_subsets, BudgetGate* bg, kp_drift_result* out, int64_t* first,
                            kp_solve_result** replacements, kp_solve_stats* stats) {
@@ -6960,8 +7117,7 @@ static int32_t DriftLocked(kp_cluster_plan* plan, kp_cancel* cancel, const uint3
     if (SeqnumsOf(plan->cp->B->catalogs) != plan->cp->B->seqnums)
       return fail(KP_E_INVAL, "stale plan: a catalogue's seqnum changed since it was prepared (kp_cluster_refresh)");
   }
-  using clk = std::chrono::steady_clock;
-  const auto t0 = clk::now();
+  const auto t0 = std::chrono::steady_clock::now();
   vector<vector<uint32_t>> cands;
   vector<int> batched, single;
   vector<char> blocked;
@@ -6971,54 +7127,32 @@ static int32_t DriftLocked(kp_cluster_plan* plan, kp_cancel* cancel, const uint3
   memset(plan->general_phase, 0, sizeof plan->general_phase);
   plan->general_ms = 0;
   plan->general_batched = 0;
-  DriftRun dr;
-  dr.host_out.assign(n_subsets, DriftOut{});
-  dr.on_host.assign(n_subsets, 0);
-  uint64_t counters[3] = {0, 0, 0}, n_launches = 0;
-  double dev_ms = 0, host_ms[2] = {0, 0};
+  GenTotals T;
+  T.batched = batched.size(), T.single = single.size();
+  DriftMode mode(plan, T, cancel, n_subsets);
   if (!batched.empty()) {
     GeneralBatch& gb = *plan->gb;
-    if (int32_t rc = DriftTables(ctx, gb, plan->cluster()->cl)) return rc;
+    if (int32_t rc = RecordTables(ctx, gb, plan->cluster()->cl)) return rc;
     if (gb.drift_out_n < n_subsets) {
       HIPCHK(gb.drift_out.alloc(sizeof(DriftOut) * n_subsets));
       gb.drift_out_n = n_subsets;
     }
-    dr.d_out = (DriftOut*)gb.drift_out.p;
-    static const vector<std::map<string, string>> no_labels;
-    vector<SimOut> no_outs;
-    if (int32_t rc = GeneralBatchRun(plan, gb, cands, batched, no_labels, 0, no_outs, counters, &dev_ms, host_ms, cancel,
-                                     &n_launches, &dr))
-      return rc;
-    // the verdicts of every launch: one copy (the launches have drained: their records were read)
-    vector<DriftOut> dev(n_subsets);
-    HIPCHK(hipMemcpyAsync(dev.data(), dr.d_out, sizeof(DriftOut) * n_subsets, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (int s : batched)
-      if (!dr.on_host[s]) dr.host_out[s] = dev[s];
+    mode.v.dev = (DriftOut*)gb.drift_out.p;
+    if (int32_t rc = GeneralBatchRun(gb, cands, batched, mode)) return rc;
+    if (int32_t rc = mode.v.Merge(ctx->stream, batched)) return rc;
   }
   for (int s : single)
-    if (int32_t rc = DriftSimOne(plan, cands[s], s, dr, counters, &dev_ms, cancel)) return rc;
-  for (uint32_t s = 0; s < n_subsets; s++)
-    if (blocked[s]) dr.host_out[s].blocked = 1, dr.host_out[s].first_unscheduled = -1;
+    if (int32_t rc = mode.SimOne(cands[s], s)) return rc;
   static_assert(sizeof(DriftOut) == sizeof(kp_drift_result), "DriftOut mirrors kp_drift_result");
-  if (out && n_subsets) memcpy(out, dr.host_out.data(), sizeof(DriftOut) * n_subsets);
-  *first = dr.first;
-  if (replacements) *replacements = dr.res.release();
-  if (stats) {
-    stats->device_ms = dev_ms;
-    stats->solve_kernel_ms = dev_ms;
-    stats->attempts = counters[0];
-    stats->bytes_algorithmic = counters[1];
-    stats->pops = counters[2];
-    stats->phase_cycles[0] = batched.size();
-    stats->phase_cycles[1] = single.size();
-    stats->phase_cycles[2] = n_launches;
-    stats->prepare_ms = plan->prepare_ms;
-    stats->host_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-  }
+  DriftOut stamp{};
+  stamp.blocked = 1, stamp.first_unscheduled = -1;
+  mode.v.Emit(blocked, stamp, out);
+  *first = mode.first;
+  if (replacements) *replacements = mode.res.release();
+  if (stats) FillStats(stats, plan, T, t0);
   if (ctx->ov.host_timing)
     fprintf(stderr, "[kp drift] %u sims (%zu batched, %zu single, %llu launches): overlays %.2f records %.2f device %.2f ms\n",
-            n_subsets, batched.size(), single.size(), (unsigned long long)n_launches, host_ms[0], host_ms[1], dev_ms);
+            n_subsets, batched.size(), single.size(), (unsigned long long)T.n_launches, T.host_ms[0], T.host_ms[1], T.dev_ms);
   return KP_OK;
 }
 
@@ -7261,69 +7395,6 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
   return KP_OK;
 }
 
-int32_t kp_cluster_simulate(kp_cluster_plan* plan, const uint32_t* offsets, const uint32_t* nodes, uint32_t n_subsets,
-                            int32_t multi_node, kp_sim_result* out, kp_solve_stats* stats) {
-  return kp_cluster_simulate_cancellable(plan, nullptr, offsets, nodes, n_subsets, multi_node, out, stats);
-}
-
-static int32_t SimulateImpl(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
-                            uint32_t n_subsets, int32_t multi_node, kp_sim_result* out, kp_solve_stats* stats,
-                            BudgetGate* bg, kp_solve_result** commands = nullptr);
-
-// The spot-to-spot branch of computeConsolidation: the replacement launches spot only, so
-// karpenter.sh/capacity-type In [spot] replaces whatever the NodeClaim required of the capacity type.
-static void NarrowToSpot(const Dict& d, KReqs& q) {
-  const int k = d.key(kCapType);
-  const int bit = k >= 0 ? d.bit(k, "spot") : -1;
-  if (bit < 0) return;
-  for (int wi = 0; wi < nwords(d, k); wi++) q.vals[kw(d, k, wi)] = 0;
-  q.vals[bit / 64] |= 1ull << (bit % 64);
-  q.present |= 1ull << k;
-  q.compl_ &= ~(1ull << k);
-  q.hgt &= ~(1ull << k), q.hlt &= ~(1ull << k), q.hmin &= ~(1ull << k);
-}
-
-// The simulation's input order and existing-node index, as kp_abi.h states them for kp_cluster_drift's replacements and
-// kp_cluster_command's commands: pending pods, the deleting nodes' pods in node order, the subset's pods in subset
-// order; the nodes neither in the subset nor being deleted, in cluster order.
-struct CommandIndex {
-  const kp_cluster& cl;
-  vector<int32_t> pod_idx;     // [P] input index of a queued pod, -1
-  vector<int32_t> del_before;  // [N + 1] deleting nodes before node i
-  vector<uint32_t> sorted;     // the current subset's nodes, ascending
-  vector<uint32_t> cand_pods;
-  int n_base = 0;
-  explicit CommandIndex(const kp_cluster& c) : cl(c), pod_idx(std::max<uint32_t>(c.n_pods, 1), -1), del_before(c.n_nodes + 1, 0) {
-    for (uint32_t j = 0; j < cl.n_pending; j++) pod_idx[cl.pending_pods[j]] = n_base++;
-    for (uint32_t i = 0; i < cl.n_nodes; i++) {
-      del_before[i + 1] = del_before[i] + (cl.nodes[i].deleting ? 1 : 0);
-      if (cl.nodes[i].deleting)
-        for (uint32_t j = 0; j < cl.nodes[i].n_pods; j++) pod_idx[cl.nodes[i].pods[j]] = n_base++;
-    }
-  }
-  int Enter(const uint32_t* cand, uint32_t n) {  // -> pods queued
-    sorted.assign(cand, cand + n);
-    std::sort(sorted.begin(), sorted.end());
-    int k = n_base;
-    for (uint32_t i = 0; i < n; i++)
-      for (uint32_t j = 0; j < cl.nodes[cand[i]].n_pods; j++) {
-        cand_pods.push_back(cl.nodes[cand[i]].pods[j]);
-        pod_idx[cand_pods.back()] = k++;
-      }
-    return k;
-  }
-  void Leave() {
-    for (uint32_t p : cand_pods) pod_idx[p] = -1;
-    cand_pods.clear();
-  }
-  int Existing(uint32_t node) const {  // -1: in the subset or being deleted
-    if (node >= cl.n_nodes || cl.nodes[node].deleting) return -1;
-    auto it = std::lower_bound(sorted.begin(), sorted.end(), node);
-    if (it != sorted.end() && *it == node) return -1;
-    return (int)node - del_before[node] - (int)(it - sorted.begin());
-  }
-};
-
 // kp_cluster_command on a plan of the batched kernel: the commands of the subsets that decided DELETE or REPLACE, from
 // the records the emitting sim_kernel left (recs: their host copy). Existing positions become the ABI's existing
 // index, queue positions the simulation's input order, the spot-to-spot narrowing is applied and the requirements
@@ -7399,27 +7470,9 @@ static int32_t BuildSimCommands(kp_cluster_plan* plan, const uint32_t* offsets, 
   return KP_OK;
 }
 
-int32_t kp_cluster_simulate_cancellable(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets,
-                                        const uint32_t* nodes, uint32_t n_subsets, int32_t multi_node, kp_sim_result* out,
-                                        kp_solve_stats* stats) {
-  return SimulateImpl(plan, cancel, offsets, nodes, n_subsets, multi_node, out, stats, nullptr);
-}
-
-int32_t kp_cluster_simulate_budgeted(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets,
-                                     const uint32_t* nodes, uint32_t n_subsets, int32_t multi_node,
-                                     const uint32_t* allowed, uint32_t n_allowed, kp_sim_result* out, uint64_t* n_blocked,
-                                     kp_solve_stats* stats) {
-  if (n_blocked) *n_blocked = 0;
-  if (!allowed) return SimulateImpl(plan, cancel, offsets, nodes, n_subsets, multi_node, out, stats, nullptr);
-  BudgetGate bg{allowed, n_allowed};
-  const int32_t rc = SimulateImpl(plan, cancel, offsets, nodes, n_subsets, multi_node, out, stats, &bg);
-  if (!rc && n_blocked) *n_blocked = bg.blocked;
-  return rc;
-}
-
 static int32_t SimulateImpl(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
                             uint32_t n_subsets, int32_t multi_node, kp_sim_result* out, kp_solve_stats* stats,
-                            BudgetGate* bg, kp_solve_result** commands) {
+                            BudgetGate* bg, kp_solve_result** commands = nullptr) {
   auto t0 = std::chrono::steady_clock::now();
   if (!plan || (n_subsets && (!offsets || !out))) return fail(KP_E_INVAL, "null argument");
   if (cancel && cancel->ctx.p != plan->ctx.p) return fail(KP_E_INVAL, "the cancel token belongs to another context");
@@ -7453,24 +7506,38 @@ static int32_t SimulateImpl(kp_cluster_plan* plan, kp_cancel* cancel, const uint
   if (em.rec)
     if (int32_t rc2 = BuildSimCommands(plan, offsets, nodes, n_subsets, out, recs.data(), em, commands)) return rc2;
   if (stats) {
-    stats->device_ms = ms;
-    stats->solve_kernel_ms = ms;
-    stats->attempts = kst[0];
-    stats->bytes_algorithmic = kst[1];
-    stats->pops = kst[2];
-    stats->phase_cycles[0] = kst[3];
-    if (plan->general) {  // general path: simulations batched / compiled per subset, batched launches
-      stats->phase_cycles[1] = kst[4];
-      stats->phase_cycles[2] = kst[6];
+    FillStats(stats, plan, TotalsOf(kst, ms), t0);
+    if (plan->general) {
       for (int k = 0; k < 8; k++) stats->attempt_cycles[k] = plan->general_phase[k];  // (timing diagnostics)
     } else {  // batched sweep: wave slots launched, most subsets any wave ran
       stats->phase_cycles[1] = plan->sim_waves[0];
       stats->phase_cycles[2] = plan->sim_waves[1];
     }
-    stats->prepare_ms = plan->prepare_ms;
-    stats->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
   return KP_OK;
+}
+
+int32_t kp_cluster_simulate_cancellable(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets,
+                                        const uint32_t* nodes, uint32_t n_subsets, int32_t multi_node, kp_sim_result* out,
+                                        kp_solve_stats* stats) {
+  return SimulateImpl(plan, cancel, offsets, nodes, n_subsets, multi_node, out, stats, nullptr);
+}
+
+int32_t kp_cluster_simulate(kp_cluster_plan* plan, const uint32_t* offsets, const uint32_t* nodes, uint32_t n_subsets,
+                            int32_t multi_node, kp_sim_result* out, kp_solve_stats* stats) {
+  return kp_cluster_simulate_cancellable(plan, nullptr, offsets, nodes, n_subsets, multi_node, out, stats);
+}
+
+int32_t kp_cluster_simulate_budgeted(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets,
+                                     const uint32_t* nodes, uint32_t n_subsets, int32_t multi_node,
+                                     const uint32_t* allowed, uint32_t n_allowed, kp_sim_result* out, uint64_t* n_blocked,
+                                     kp_solve_stats* stats) {
+  if (n_blocked) *n_blocked = 0;
+  if (!allowed) return SimulateImpl(plan, cancel, offsets, nodes, n_subsets, multi_node, out, stats, nullptr);
+  BudgetGate bg{allowed, n_allowed};
+  const int32_t rc = SimulateImpl(plan, cancel, offsets, nodes, n_subsets, multi_node, out, stats, &bg);
+  if (!rc && n_blocked) *n_blocked = bg.blocked;
+  return rc;
 }
 
 int32_t kp_cluster_command(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
@@ -7539,63 +7606,18 @@ static int32_t ValidateCompile(const vector<const kp_catalog*>& cats, int TW, co
   return KP_OK;
 }
 
-// A subset compiled on its own (GeneralSolveOne: SimulateScheduling's Problem compiled from the subset, run as a whole
-// Solve): the rule applied to that Solve's result on the host. kp_solve_run has applied the held reservations and
-// Truncate's minValues check to the NodeClaim (HostMinValuesOK: options cleared, pods unplaced).
-static int32_t ValidateSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand, int s, ValRun& vl, uint64_t* counters,
-                              double* dev_ms, kp_cancel* cancel) {
-  SimOneSolve so;
-  if (int32_t rc = GeneralSolveOne(plan, cand, so, counters, dev_ms, cancel)) return rc;
-  const kp_cluster& cl = plan->cluster()->cl;
-  const kp_solve_result* res = so.res.get();
-  const bool repl = vl.checks[s].decision == KP_DECISION_REPLACE;
-  ValOut& v = vl.host_out[s];
-  memset(&v, 0, sizeof v);
-  vl.on_host[s] = 1;
-  v.n_pods = (uint32_t)so.kind.size();
-  if (res->ncs.size() > 1) {
-    v.verdict = KP_INVALID_MULTIPLE;
-    v.n_nodeclaims = 2;
-    return KP_OK;
-  }
-  v.n_nodeclaims = (uint32_t)res->ncs.size();
-  for (size_t p = 0; p < so.kind.size(); p++) {
-    const int32_t pl = res->placement[p];
-    if (so.kind[p] == 2) continue;
-    if (pl == -1 || (so.kind[p] == 0 && pl <= -2 && !so.ex[(size_t)(-2 - pl)].initialized)) v.n_unscheduled++;
-  }
-  if (v.n_unscheduled) {
-    v.verdict = KP_INVALID_UNSCHEDULED;
-  } else if (res->ncs.empty()) {
-    v.verdict = repl ? KP_INVALID_NO_REPLACEMENT_NEEDED : KP_VALID;
-  } else if (!repl) {
-    v.verdict = KP_INVALID_NEEDS_REPLACEMENT;
-  } else {
-    const vector<HostType>& types = cl.catalogs[res->nc_cat[0]]->types;
-    std::set<string> have;
-    for (uint32_t t : res->ncs[0].options)
-      if (t < types.size()) have.insert(types[t].name);
-    for (const string& nm : vl.names[s])
-      if (!have.count(nm)) v.n_missing++;
-    v.verdict = v.n_missing ? KP_INVALID_NOT_SUBSET : KP_VALID;
-  }
-  return KP_OK;
-}
-
-// General-path plans. Batched subsets: solve_kernel (stop at the second NodeClaim), finalize_kernel,
-// validate_verdict_kernel and validate_sum_kernel per launch (GeneralBatchRun); a launch downloads its record, the
-// verdicts come back in one copy at the end. Subsets compiled on their own: ValidateSimOne.
+// General-path plans (ValidateMode). Batched subsets: solve_kernel (stop at the second NodeClaim), finalize_kernel,
+// validate_verdict_kernel and validate_sum_kernel per launch; a launch downloads its record, the verdicts come back in
+// one copy at the end. Subsets compiled on their own: the mode's SimOne.
 static int32_t ValidateGeneralLocked(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
                                      uint32_t n_subsets, const kp_command_check* checks, BudgetGate* bg, kp_validation* out,
-                                     uint64_t* counters, double* dev_ms, uint64_t* kst) {
+                                     GenTotals& T) {
   kp_ctx* ctx = plan->ctx;
   if (cancel && __atomic_load_n(cancel->flag, __ATOMIC_SEQ_CST))
     return fail(KP_E_CANCELED, "cancelled before the simulations");
-  ValRun vl;
-  vl.checks = checks;
-  vl.names.resize(n_subsets);
+  ValidateMode mode(plan, T, cancel, checks, n_subsets);
   for (uint32_t s = 0; s < n_subsets; s++)
-    if (int32_t rc = CheckNames(checks[s], s, vl.names[s])) return rc;
+    if (int32_t rc = CheckNames(checks[s], s, mode.names[s])) return rc;
   vector<vector<uint32_t>> cands;
   vector<int> batched, single;
   vector<char> blocked;
@@ -7608,14 +7630,11 @@ static int32_t ValidateGeneralLocked(kp_cluster_plan* plan, kp_cancel* cancel, c
     std::sort(single.begin(), single.end());
     batched.clear();
   }
-  vl.host_out.assign(n_subsets, ValOut{});
-  vl.on_host.assign(n_subsets, 0);
-  uint64_t n_launches = 0;
-  double host_ms[2] = {0, 0};
+  T.batched = batched.size(), T.single = single.size();
   DevBuf dev;  // the compiled checks and the verdict records of this call
   if (!batched.empty()) {
     GeneralBatch& gb = *plan->gb;
-    if (int32_t rc = DriftTables(ctx, gb, plan->cluster()->cl)) return rc;
+    if (int32_t rc = RecordTables(ctx, gb, plan->cluster()->cl)) return rc;
     ValCheck vc;
     if (int32_t rc = ValidateCompile(gb.C->B->catalogs, gb.C->B->TW, checks, n_subsets, vc)) return rc;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -7629,32 +7648,18 @@ static int32_t ValidateGeneralLocked(kp_cluster_plan* plan, kp_cancel* cancel, c
     HIPCHK(hipMemcpyAsync(db + o_rep, vc.replace.data(), n_subsets, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(db + o_out, 0, sizeof(ValOut) * n_subsets, st));
     HIPCHK(hipStreamSynchronize(st));  // (the launches run on the batch's own streams)
-    vl.d_want = (const uint64_t*)db;
-    vl.d_unknown = (const uint32_t*)(db + o_unk);
-    vl.d_replace = db + o_rep;
-    vl.d_out = (ValOut*)(db + o_out);
-    static const vector<std::map<string, string>> no_labels;
-    vector<SimOut> no_outs;
-    if (int32_t rc = GeneralBatchRun(plan, gb, cands, batched, no_labels, 0, no_outs, counters, dev_ms, host_ms, cancel,
-                                     &n_launches, nullptr, nullptr, &vl))
-      return rc;
-    vector<ValOut> got(n_subsets);
-    HIPCHK(hipMemcpyAsync(got.data(), vl.d_out, sizeof(ValOut) * n_subsets, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (int s : batched)
-      if (!vl.on_host[s]) vl.host_out[s] = got[s];
+    mode.d_want = (const uint64_t*)db;
+    mode.d_unknown = (const uint32_t*)(db + o_unk);
+    mode.d_replace = db + o_rep;
+    mode.v.dev = (ValOut*)(db + o_out);
+    if (int32_t rc = GeneralBatchRun(gb, cands, batched, mode)) return rc;
+    if (int32_t rc = mode.v.Merge(st, batched)) return rc;
   }
   for (int s : single)
-    if (int32_t rc = ValidateSimOne(plan, cands[s], s, vl, counters, dev_ms, cancel)) return rc;
-  for (uint32_t s = 0; s < n_subsets; s++) {
-    if (blocked[s]) {
-      memset(&vl.host_out[s], 0, sizeof(ValOut));
-      vl.host_out[s].verdict = KP_INVALID_BUDGET;
-      vl.host_out[s].blocked = 1;
-    }
-  }
-  memcpy(out, vl.host_out.data(), sizeof(ValOut) * n_subsets);
-  kst[3] = batched.size(), kst[4] = single.size(), kst[6] = n_launches;
+    if (int32_t rc = mode.SimOne(cands[s], s)) return rc;
+  ValOut stamp{};
+  stamp.verdict = KP_INVALID_BUDGET, stamp.blocked = 1;
+  mode.v.Emit(blocked, stamp, out);
   return KP_OK;
 }
 
@@ -7674,17 +7679,11 @@ int32_t kp_cluster_validate(kp_cluster_plan* plan, kp_cancel* cancel, const uint
   if (bg)
     if (int32_t rc = CheckBudget(plan, bg)) return rc;
   if (n_subsets == 0) return KP_OK;
-  uint64_t kst[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  float ms = 0;
+  GenTotals T;
   if (plan->general) {
-    uint64_t counters[3] = {0, 0, 0};
-    double dev_ms = 0;
     gate.blocked = 0;
     memset(plan->general_phase, 0, sizeof plan->general_phase);
-    if (int32_t rc = ValidateGeneralLocked(plan, cancel, offsets, nodes, n_subsets, checks, bg, out, counters, &dev_ms, kst))
-      return rc;
-    kst[0] = counters[0], kst[1] = counters[1], kst[2] = counters[2];
-    ms = (float)dev_ms;
+    if (int32_t rc = ValidateGeneralLocked(plan, cancel, offsets, nodes, n_subsets, checks, bg, out, T)) return rc;
   } else {
     if (int32_t rc = CatalogsAlive(plan->cp->B->alive)) return rc;
     ValCheck vc;
@@ -7693,12 +7692,15 @@ int32_t kp_cluster_validate(kp_cluster_plan* plan, kp_cancel* cancel, const uint
     if (int32_t rc = SimLaunchLocked(plan, offsets, nodes, n_subsets, 0, a, cancel, bg, nullptr, &vc)) return rc;
     hipStream_t st = ctx->stream;
     vector<uint8_t> gbytes(bg ? n_subsets : 0);
+    uint64_t kst[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    float ms = 0;
     HIPCHK(hipMemcpyAsync(out, vc.val, sizeof(ValOut) * n_subsets, hipMemcpyDeviceToHost, st));
     if (bg) HIPCHK(hipMemcpyAsync(gbytes.data(), vc.gate, n_subsets, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(kst, a.stats, sizeof kst, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (kst[5]) return fail(KP_E_CANCELED, "validation simulations cancelled (kp_cancel_set)");
     HIPCHK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    T = TotalsOf(kst, ms);
     for (uint32_t s = 0; s < n_subsets; s++) {
       if (bg && !gbytes[s]) {  // not simulated
         memset(&out[s], 0, sizeof out[s]);
@@ -7711,46 +7713,28 @@ int32_t kp_cluster_validate(kp_cluster_plan* plan, kp_cancel* cancel, const uint
     // NodePool limits: sim_kernel stops where a pod would open a second NodeClaim, judged by the limits the pass began
     // with. The first NodeClaim has taken its largest option out of its pool's remaining limits (subtractMax), so that
     // second NodeClaim may no longer exist and the pod fail instead. Such a record is settled by the subset's own
-    // whole Solve (ValidateSimOne); every other record is exact as the kernel left it.
+    // whole Solve (ValidateMode::SimOne); every other record is exact as the kernel left it.
     bool limited = false;
     for (uint32_t lp : plan->cp->tmpl_limit_present) limited = limited || lp != 0;
     if (limited) {
       if (!plan->cluster()) return fail(KP_E_INVAL, "the plan keeps no cluster");
-      ValRun vl;
-      vl.checks = checks;
-      vl.names.resize(n_subsets);
-      vl.host_out.assign(n_subsets, ValOut{});
-      vl.on_host.assign(n_subsets, 0);
-      uint64_t counters[3] = {0, 0, 0};
-      double dev_ms = 0;
+      ValidateMode mode(plan, T, cancel, checks, n_subsets);  // (its counters and device time add to the sweep's)
       for (uint32_t s = 0; s < n_subsets; s++) {
         if (out[s].verdict != KP_INVALID_MULTIPLE) continue;
-        if (int32_t rc = CheckNames(checks[s], s, vl.names[s])) return rc;
+        if (int32_t rc = CheckNames(checks[s], s, mode.names[s])) return rc;
         const vector<uint32_t> cand(nodes + offsets[s], nodes + offsets[s + 1]);
-        if (int32_t rc = ValidateSimOne(plan, cand, (int)s, vl, counters, &dev_ms, cancel)) return rc;
-        memcpy(&out[s], &vl.host_out[s], sizeof out[s]);
+        if (int32_t rc = mode.SimOne(cand, (int)s)) return rc;
+        memcpy(&out[s], &mode.v.host[s], sizeof out[s]);
       }
-      kst[0] += counters[0], kst[1] += counters[1], kst[2] += counters[2];
-      ms += (float)dev_ms;
     }
   }
   if (n_blocked && bg) *n_blocked = gate.blocked;
   if (stats) {
-    stats->device_ms = ms;
-    stats->solve_kernel_ms = ms;
-    stats->attempts = kst[0];
-    stats->bytes_algorithmic = kst[1];
-    stats->pops = kst[2];
-    stats->phase_cycles[0] = kst[3];
-    if (plan->general) {
-      stats->phase_cycles[1] = kst[4];
-      stats->phase_cycles[2] = kst[6];
-    } else {
+    FillStats(stats, plan, T, t0);
+    if (!plan->general) {
       stats->phase_cycles[1] = plan->sim_waves[0];
       stats->phase_cycles[2] = plan->sim_waves[1];
     }
-    stats->prepare_ms = plan->prepare_ms;
-    stats->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
   return KP_OK;
 }

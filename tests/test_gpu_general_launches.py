@@ -283,3 +283,63 @@ def test_after_a_cancelled_call(ctx, spread, plan, prod, ov):
     assert st["phase_cycles"][:3] == [len(subs), 0, _ceil(len(subs), 7)]
     _assert_oracle(res, oracle)
     assert (res == prod[0]).all()
+
+
+def test_modes_share_slots(ctx, spread, ov):
+    """One plan's two launch slots (arenas, argument blocks, record buffer, pinned buffers) serve every result mode of
+    the launch loop. On one fresh plan, 7 simulations per launch (9 launches a call, each slot reused at least 4
+    times): simulate, drift, command, validate (checks taken from the commands just returned, so every subset that
+    decided is valid), simulate again. Each call's whole output equals the same call made first on a fresh plan of its
+    own, and both simulate calls equal the oracle."""
+    import kpamd
+    import command_ref
+    import validate_ref as vr
+    from test_gpu_command import _bits
+    cl, subs, oracle = spread
+    offs, flat = _csr(subs)
+    ov(general_launch=7)
+    shape = [len(subs), 0, _ceil(len(subs), 7)]
+    assert shape[2] == 9
+
+    def simulate(p):
+        res, st = p.simulate_csr(offs, flat)
+        assert st["phase_cycles"][:3] == shape
+        _assert_oracle(res, oracle)
+        return res.tobytes()
+
+    def drift(p):
+        d = p.drift(subs, read_all=True)
+        assert d["stats"]["phase_cycles"][:3] == shape
+        return d["results"], d["first"], d["blocked"], command_ref.command_fields(d["replacements"])
+
+    def command(p):
+        sims, cmds, st = p.command(subs, multi_node=True)
+        assert st["phase_cycles"][:3] == shape
+        return [_bits(d) for d in sims], [command_ref.command_fields(c) for c in cmds], cmds
+
+    def validate(p, cmds):
+        checks = [vr.check_of(cl, c) if c is not None else {"decision": vr.DELETE} for c in cmds]
+        got, st = p.validate(subs, checks)
+        assert st["phase_cycles"][:3] == shape
+        return got
+
+    def alone(call, *args):
+        p = kpamd.ClusterPlan(ctx, cl)
+        try:
+            return call(p, *args)
+        finally:
+            p.close()
+
+    shared = kpamd.ClusterPlan(ctx, cl)
+    try:
+        assert simulate(shared) == alone(simulate)
+        assert drift(shared) == alone(drift)
+        sims, fields, cmds = command(shared)
+        assert (sims, fields) == alone(command)[:2]
+        assert any(c is not None for c in cmds) and any(c is None for c in cmds)
+        verdicts = validate(shared, cmds)
+        assert verdicts == alone(validate, cmds)
+        assert all(v["verdict"] == vr.VALID for v, c in zip(verdicts, cmds) if c is not None)
+        assert simulate(shared) == alone(simulate)
+    finally:
+        shared.close()
