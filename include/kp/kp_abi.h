@@ -412,7 +412,10 @@ typedef struct kp_solve_stats {
   uint64_t reserved_offering_errors; /* ABI v9: pops whose addToNewNodeClaim failed on a ReservedOfferingError (strict
                                         mode; upstream Results.ReservedOfferingErrors: deferred, not relaxed) */
   uint64_t run_length_pods; /* ABI v11: pods the fast lane committed as part of a run (queue runs of one shape-level
-                               onto one NodeClaim, committed k at a time: solve_kernel's run-length commit) */
+                               onto one NodeClaim, committed k at a time: solve_kernel's run-length commit; with the
+                               open set, the pods its loop placed on the NodeClaim of the pod before them: those it
+                               places on another open NodeClaim are not counted, so the figure stays bounded by the
+                               queue neighbours of one request row on one NodeClaim) */
   uint64_t order_chunks[5]; /* ABI v10, diagnostic: the chunked newNodeClaims order past the LDS sort capacity: peak
                                chunks, chunk splits, emptied chunks, directory (re)builds, final order mode (1 LDS,
                                2 chunked, 0 flat global) */
@@ -436,9 +439,11 @@ int32_t kp_ctx_create(const kp_options* opts, kp_ctx** out);
 typedef struct kp_overrides {
   int32_t fast_lane;           /* 0 auto (the run-length-commit variant where most queue neighbours share their shape),
                                   1 the plain variant, 2 the run-length-commit variant with the continuation round,
-                                  3 the run-length-commit variant without it (the one auto picks for queue runs of
-                                  different shapes with one request row). Solves for which 2 or 3 is not built
-                                  (topology, existing nodes, a spilled order) run the plain variant */
+                                  3 the run-length-commit variant without it, 4 (the one auto picks for queue runs of
+                                  different shapes with one request row) variant 3 with the open set in place of
+                                  the closed-form commit: the entries after an append are placed one at a time on the
+                                  last few NodeClaims committed to, from state held on chip. Solves for which 2, 3 or
+                                  4 is not built (topology, existing nodes, a spilled order) run the plain variant */
   int32_t sort_capacity;       /* 0: 8192 NodeClaims in the LDS order; n > 0: the chunked order past n NodeClaims */
   int32_t chunk_capacity;      /* 0: the chunked order's full directory; n > 0: at most n chunks (then the flat order);
                                   n < 0: no chunks (the flat order past sort_capacity) */

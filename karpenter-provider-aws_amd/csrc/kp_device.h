@@ -117,7 +117,8 @@ struct SolveArgs {
   const int32_t* cancel;             // kp_cancel flag (host-mapped, polled every ~1024 pops), NULL: none
   int32_t cont;                      // the fast lane variant: 1 with the continuation round and the run-length commit
                                      // (queue runs of one shape), 2 with the run-length commit alone (runs of shapes
-                                     // with one request row), 0 neither
+                                     // with one request row), 3 as 2 with the open set's sequential loop in place of the
+                                     // closed-form commit (runs across several NodeClaims being filled), 0 neither
   // topology spread (upstream Topology, TopologyTypeSpread groups). A group on a dictionary key keeps a
   // count per value ordinal and the mask of registered domains; a hostname group a saturating u8 count per
   // node (existing positions: hcnt_ex, NodeClaim ids: hcnt_nc).

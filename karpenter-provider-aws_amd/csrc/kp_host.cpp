@@ -1315,7 +1315,7 @@ struct Compiled {
   vector<int64_t> tmpl_remaining;
   // shapes
   vector<int32_t> shape_level_base, shape_nlevels;
-  int32_t cont_hint = 0;  // SolveArgs::cont: 1 most queue neighbours share their shape, 2 their request class
+  int32_t cont_hint = 0;  // SolveArgs::cont: 1 most queue neighbours share their shape, 3 their request class
   vector<KReqs> shape_reqs;
   vector<uint64_t> shape_negop, shape_tolerates;  // per shape-level (tolerations change at the PreferNoSchedule level)
   vector<char> sl_pns;                             // per shape-level: toleratePreferNoScheduleTaints' level
@@ -2949,8 +2949,11 @@ int32_t CompilePerCall(const kp_solve_in* in, const SolveRaw& raw, Compiled& cp)
     }
     const bool runs = 2 * same >= in->n_pods;
     const bool mixed_runs = 2 * same_rc >= in->n_pods && cp.n_rclass < (int32_t)in->n_shapes;
-    // (2: the run-length commit without the continuation round, which only pays inside runs of one shape)
-    cp.cont_hint = in->n_pods <= 1 ? 0 : runs ? 1 : mixed_runs ? 2 : 0;
+    // (3: no continuation round, which only pays inside runs of one shape, and the open set's sequential loop in
+    // place of the closed-form commit: the neighbours of one class mostly alternate between a few NodeClaims, which
+    // the closed form on one NodeClaim cannot follow; config 2's kernel 160.3 -> 133.8 ms, measured. 2 stays built for
+    // kp_overrides.fast_lane 3)
+    cp.cont_hint = in->n_pods <= 1 ? 0 : runs ? 1 : mixed_runs ? 3 : 0;
   }
   pt.lap(" queue");
   return KP_OK;
@@ -3435,10 +3438,10 @@ void BindSolve(SolveArgs& a, const Compiled& C, const SolveOffs& o, uint8_t* sh,
   a.req_res_mask = rmask;
   a.n_req_res = __builtin_popcount(rmask);
   a.timing = C.ov.timing ? 1 : 0;
-  // kp_overrides.fast_lane: 1 plain, 2 cont 1, 3 cont 2. solve_kernel's dispatch takes a forced value as it takes the
-  // hint: cont 1 and cont 2 are instantiated for the LDS order without topology and without existing nodes only, and
+  // kp_overrides.fast_lane: 1 plain, 2 cont 1, 3 cont 2, 4 cont 3. solve_kernel's dispatch takes a forced value as it takes
+  // the hint: cont 1 to 3 are instantiated for the LDS order without topology and without existing nodes only, and
   // every other Solve (topology, existing nodes, the chunked or flat order from the spill on) runs CONT 0
-  a.cont = C.ov.fast_lane ? (C.ov.fast_lane == 2 ? 1 : C.ov.fast_lane == 3 ? 2 : 0) : C.cont_hint;
+  a.cont = C.ov.fast_lane ? (C.ov.fast_lane == 2 ? 1 : C.ov.fast_lane == 3 ? 2 : C.ov.fast_lane == 4 ? 3 : 0) : C.cont_hint;
   a.n_groups = C.G;
   a.tg_key = (const int32_t*)(sh + o.tgk);
   a.tg_row = (const int32_t*)(sh + o.tgr);

@@ -36,7 +36,7 @@
 #if !defined(KP_DIAG_BUILD) &&                                                                                       \
     (defined(FASTLANE) || defined(FL_NOTIME) || defined(FT_FINE) || defined(FAST_SCAN_MAX) ||                        \
      defined(FAST_CHK_LIVE) || defined(FAST_EX_ROUNDS) || defined(FAST_CONT) || defined(SORT_DIAG) || defined(EX_DIAG) || defined(FX_DIAG) || defined(FEAS_MAX_BLOCKS) ||                 \
-     defined(REQ_CLASSES) || defined(MERGE_DIAG) ||                 \
+     defined(REQ_CLASSES) || defined(MERGE_DIAG) || defined(OS_DIAG) ||                 \
      defined(FEASQ_EW) || defined(FEASQ_ROWS) || defined(FEASQ_B128) || defined(FEASQ_SKIP_EVAL) || defined(FL_SKIP) ||  \
      defined(SIM_WPE) || defined(FEASQ_MINW))
 #error "a measurement knob is set outside a tools/ variant build (tools/kp_diag.h)"
@@ -1592,7 +1592,7 @@ __device__ __forceinline__ void record_write(const RecRead& r, int g, int aux, u
 // partialInsertionSort) and the moved NodeClaim's new place is within the window, the ids already in registers
 // are written back shifted. Returns the cursor clamp (p), or -2: the general replay (sort_newnodeclaims_wave).
 __device__ __forceinline__ int sort_mut1_window(LdsI32 ord, LdsI32 npods, int n, int p, int cap,
-                                                 bool* moved = nullptr) {
+                                                 bool* moved = nullptr, int* qout = nullptr) {
   const int lane = LANE;
   const int i = p + lane;
   const int t = lane / 3;
@@ -1620,6 +1620,7 @@ __device__ __forceinline__ int sort_mut1_window(LdsI32 ord, LdsI32 npods, int n,
   const uint64_t ge = __ballot(lane > 0 && (i >= n || key >= K));
   if (!ge) return -2;  // the tie run continues past the window
   const int q = __builtin_ctzll(ge);  // elements p+1 .. p+q-1 move left by one, the mutated one lands at p+q-1
+  if (qout) *qout = q;
   wave_sync();
   if (lane >= 1 && lane < q) ord[i - 1] = id;
   const int elem = __builtin_amdgcn_readfirstlane(id);
@@ -2248,13 +2249,308 @@ __device__ __forceinline__ T ka_read(uint32_t k0, uint32_t k1, uint32_t k2, uint
   }
 }
 
+// ---- the open set (fast_lane CONT 3) ---------------------------------------------------------------------------
+// Nearly every pod of a sorted queue joins one of a handful of NodeClaims the wave itself wrote a few pods ago. The
+// open set keeps the last OS_K NodeClaims this fast_lane call committed an append to in LDS, as the commit left them
+// (what fast_lane's c_* registers hold for one NodeClaim), and fl_open_set pops the window entries that follow an
+// append commit one at a time, placing each on an open NodeClaim without reading global memory for the placement.
+// An entry is taken only when the pod loop would take exactly these steps for it; otherwise the loop stops before it.
+//
+// First fit: per window entry j the set tracks a cursor C_j with the invariant "every NodeClaim at a position below
+// C_j that is not open rejects entry j's level, and is unchanged since it did". It starts as the pod loop's scan start
+// min(cursor position, lowest position mutated since the cursor's stamp), below which every NodeClaim rejected and is
+// unchanged. Only open NodeClaims change while the set lives, and those are evaluated from their LDS state for every
+// entry, so the invariant survives commits; sort.Slice's stable move of the committed (open) NodeClaim from p to
+// p + q - 1 shifts the NodeClaims in between down by one, so a C_j in (p, p + q - 1] moves down by one with them; an
+// eviction makes a NodeClaim of unknown standing, so every C_j is clamped to its position. The winner is the
+// lowest-positioned open NodeClaim at or below C_j that does not reject; it must be tagged with the level
+// (nc_fail >= NC_MERGED) and pass Fits, else the pod loop takes the entry.
+//
+// Between two calls the set stays valid only across exactly one pod-loop iteration that made one attempt, an append
+// (OpenSet::pops / att): that iteration replays no mutation (the loop below leaves none pending when it keeps the
+// set), writes one NodeClaim (which enters the set from the c_* registers) and one cursor, and no failure memo.
+#define OS_K 4
+// why the loop stops: another request class; a level not tagged on the winner (a full Add); the scan reaches a NodeClaim
+// outside the set; Fits empties the remaining types; the literal pdqsort; the window's end or a Queue.Pop stop
+enum { OS_STOP_CLASS = 0, OS_STOP_UNKNOWN, OS_STOP_NONOPEN, OS_STOP_XZERO, OS_STOP_SORT, OS_STOP_WINDOW, OS_STOP_N };
+struct OpenSet {
+  int32_t n, pops, att, win, clock;  // entries; fast_lane's pops / attempts after the last call; its window; LRU clock
+  int32_t arg[16];                   // the call's uniform arguments (fast_lane's registers) ...
+  int64_t arg_r[4];                  // ... and the committed NodeClaim's headroom
+  int32_t ret[6];                    // pending mutation and its position, the mutation stack's size / time / lost;
+                                     // [5] the pods placed on the NodeClaim of the pod before them (run_length_pods)
+  uint32_t nb[3];                    // fits_lean's byte-model units (NbUnits), folded in when fast_lane returns
+  uint32_t stops[OS_STOP_N];         // diagnostic: why the loop stopped
+  int32_t nc[OS_K], pos[OS_K], ver[OS_K], ts[OS_K], last[OS_K];
+  int64_t r[4][OS_K];                // headroom of the first four requested resources (NcHead)
+  int64_t q[OS_K][KP_NRES];          // requests
+  int32_t fj[OS_K][KP_NRES];         // Fits threshold indices
+  uint64_t X[OS_K][KP_MAX_WORDS];    // remaining types
+  int32_t memo[OS_K][64];            // nc_fail[level of window entry j][NodeClaim]
+  int32_t cur[64];                   // C_j
+  int32_t out_pod[64], out_nc[64];   // the placements of one call, in queue order
+};
+__shared__ OpenSet g_os;
+#ifndef OS_DIAG
+#define OS_DIAG 0  // diagnostic: why the open-set loop stopped (OS_STOP_*: calls per reason) in stats[25..30]
+#endif
+
+// Returns the number of window entries popped and placed (at most 63). Arguments as fast_lane's; the lane values are
+// the committed NodeClaim's c_X / c_q / c_fj, the pod's requests and the window.
+__device__ __noinline__ int fl_open_set(uint64_t kargs, int32_t LDS* s_dyn_arg, uint64_t c_X, int64_t c_q, int32_t c_fj,
+                                        int64_t preq_lane, int qw_pod, int qw_sl, int qw_epoch, int qw_lastlen) {
+  uint32_t s_dyn_off = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)s_dyn_arg);
+  asm volatile("" : "+s"(s_dyn_off));
+  int32_t LDS* s_dyn = (int32_t LDS*)(uintptr_t)s_dyn_off;
+  const uint32_t klo = __builtin_amdgcn_readfirstlane((uint32_t)kargs);
+  const uint32_t khi = __builtin_amdgcn_readfirstlane((uint32_t)(kargs >> 32));
+  const KARG SolveArgs* A = (const KARG SolveArgs*)(((uint64_t)khi << 32) | klo);
+  const DevDict& D = g_D;
+  OpenSet LDS* O = (OpenSet LDS*)&g_os;
+  FastState LDS* S = (FastState LDS*)&g_fast;
+  int32_t LDS* stk0 = (int32_t LDS*)g_stk[0];
+  const int lane = LANE;
+  const int off = U(O->arg[0]), qw_n = U(O->arg[1]), qw_head = U(O->arg[2]), epoch = U(O->arg[3]), q_len = U(O->arg[4]);
+  const int n_nc = U(O->arg[5]), wpos = U(O->arg[6]), placed = U(O->arg[7]), sl = U(O->arg[8]), c_ts = U(O->arg[9]);
+  const int c_ver = U(O->arg[10]), pops = U(O->arg[14]), att = U(O->arg[15]);
+  int stk_n = U(O->arg[11]), stk_t = U(O->arg[12]), stk_lost = U(O->arg[13]);
+  const int64_t c_r0 = (int64_t)U64((uint64_t)O->arg_r[0]), c_r1 = (int64_t)U64((uint64_t)O->arg_r[1]);
+  const int64_t c_r2 = (int64_t)U64((uint64_t)O->arg_r[2]), c_r3 = (int64_t)U64((uint64_t)O->arg_r[3]);
+  // the requested resources, as fast_lane derives them (at most four here: the caller's condition)
+  const uint32_t rmask_all = A->req_res_mask;
+  const int rr0 = rmask_all ? __builtin_ctz(rmask_all) : 0;
+  const uint32_t rm1 = rmask_all & (rmask_all - 1);
+  const int rr1 = rm1 ? __builtin_ctz(rm1) : rr0;
+  const int rk2 = kth_res(rmask_all, 2), rk3 = kth_res(rmask_all, 3);
+  const bool four = rk2 >= 0;
+  const uint32_t pr_idx = (uint32_t)(rmask_all ? rr0 : 63) | (uint32_t)(rm1 ? rr1 : 63) << 8 |
+                          (uint32_t)(rk2 >= 0 ? rk2 : 63) << 16 | (uint32_t)(rk3 >= 0 ? rk3 : 63) << 24;
+  uint32_t rrp = 0;
+  int n_rrp = 0;
+  for (uint32_t m = rmask_all; m; m &= m - 1) {
+    if (n_rrp < 4) rrp |= (uint32_t)__builtin_ctz(m) << (8 * n_rrp);
+    n_rrp++;
+  }
+  const int64_t pr0 = lane_bcast_i64(preq_lane, pr_idx & 0xff), pr1 = lane_bcast_i64(preq_lane, (pr_idx >> 8) & 0xff);
+  const int64_t pr2 = lane_bcast_i64(preq_lane, (pr_idx >> 16) & 0xff), pr3 = lane_bcast_i64(preq_lane, pr_idx >> 24);
+  const int TW = D.TW, ncc = A->ncc, cap = A->sort_cap;
+  const LdsI32 ord = (LdsI32)s_dyn;
+  const LdsI32 npods = (LdsI32)(s_dyn + cap);
+  int32_t* const cur_nc = A->cur_nc;
+  const int32_t GLB* const nc_fail = (const int32_t GLB*)A->nc_fail;
+
+  // the set as the last call left it (lane k: entry k), kept across exactly one clean pod-loop iteration
+  const int kl = min(lane, OS_K - 1);
+  int n = U(O->n);
+  const bool keep = n > 0 && U(O->pops) + 1 == pops && U(O->att) + 1 == att;
+  const bool regather = !keep || U(O->win) != qw_head;
+  if (!keep) n = 0;
+  int clock = keep ? U(O->clock) : 0;
+  int e_nc = O->nc[kl], e_pos = O->pos[kl], e_ver = O->ver[kl], e_ts = O->ts[kl], e_last = O->last[kl], e_dirty = 0;
+  int64_t e_r0 = O->r[0][kl], e_r1 = O->r[1][kl], e_r2 = O->r[2][kl], e_r3 = O->r[3][kl];
+  if (lane >= n) e_nc = -1, e_pos = INT32_MAX;
+  int C = O->cur[lane];
+  // the NodeClaim the pod loop just committed to enters (or is refreshed) from the c_* registers
+  const uint64_t hit = __ballot(lane < n && e_nc == placed);
+  int slot, evict_pos = INT32_MAX;
+  if (hit) {
+    slot = __builtin_ctzll(hit);
+  } else if (n < OS_K) {
+    slot = n++;
+  } else {  // the least recently committed leaves (every entry is clean between calls)
+    slot = 0;
+    for (int k = 1; k < OS_K; k++)
+      if (__builtin_amdgcn_readlane(e_last, k) < __builtin_amdgcn_readlane(e_last, slot)) slot = k;
+    evict_pos = __builtin_amdgcn_readlane(e_pos, slot);
+  }
+  clock += 1;
+  if (lane == slot) {
+    e_nc = placed, e_pos = wpos, e_ver = c_ver, e_ts = c_ts, e_last = clock;
+    e_r0 = c_r0, e_r1 = c_r1, e_r2 = c_r2, e_r3 = c_r3;
+  }
+  O->X[slot][lane] = c_X;
+  if (lane < KP_NRES) {
+    O->q[slot][lane] = c_q;
+    O->fj[slot][lane] = c_fj;
+  }
+  {
+    const int gsl = lane < qw_n ? qw_sl : sl;  // (gathers at valid indices)
+    if (regather) {
+      const int2 cu = *reinterpret_cast<const int2*>(&cur_nc[2 * gsl]);
+      int32_t m_r[OS_K];
+#pragma unroll
+      for (int k = 0; k < OS_K; k++) {
+        const int nck = k < n ? __builtin_amdgcn_readlane(e_nc, k) : 0;
+        m_r[k] = nc_fail[(size_t)gsl * ncc + min(nck, ncc - 1)];
+      }
+#pragma unroll
+      for (int k = 0; k < OS_K; k++) {
+        const int nck = k < n ? __builtin_amdgcn_readlane(e_nc, k) : 0;
+        O->memo[k][lane] = nck < ncc ? m_r[k] : -2;
+      }
+      C = min(cu.x, mstack_query(stk0, stk_n, stk_lost, cu.y));  // (per lane: the stamps differ)
+      if (qw_sl == sl) C = wpos;  // (the cursor the pod loop stored for this commit)
+    } else {
+      if (!hit) {
+        const int32_t m_r = nc_fail[(size_t)gsl * ncc + min(placed, ncc - 1)];
+        O->memo[slot][lane] = placed < ncc ? m_r : -2;
+      }
+      if (qw_sl == sl) C = max(C, wpos);  // the pod loop's scan: every position below wpos rejected the level
+      C = min(C, evict_pos);
+    }
+  }
+  wave_sync();
+
+  NbUnits fnb{0, 0, 0};
+  const int rc = U(S->qw_rc[off]);
+  int k = 0, mut = 1, mut_p = wpos, stop = 0;
+  // run_length_pods keeps its meaning (kp_abi.h): pods committed in a run onto the NodeClaim of the pod before them,
+  // which is all the closed-form commit takes; the pods this loop places on another open NodeClaim are not counted
+  int n_same = 0, prev_nc = placed;
+  for (;;) {
+    const int e = off + 1 + k;
+    if (e >= qw_n) {
+      stop = OS_STOP_WINDOW;
+      break;
+    }
+    // Queue.Pop would stop at an entry last pushed at the length it would pop it at (lastLen)
+    if (__builtin_amdgcn_readlane(qw_epoch, e) == epoch && __builtin_amdgcn_readlane(qw_lastlen, e) == q_len - k) {
+      stop = OS_STOP_WINDOW;
+      break;
+    }
+    if (mut) {  // sort.Slice after the previous commit, as the pod loop replays it at the next pop
+      bool moved = false;
+      int q = 0;
+      const int low = sort_mut1_window(ord, npods, n_nc, mut_p, cap, &moved, &q);
+      if (UNLIKELY(low == -2)) {  // the literal pdqsort or a long shift: the pod loop's, the mutation pending
+        stop = OS_STOP_SORT;
+        break;
+      }
+      mut = 0;
+      mstack_push_reg(stk0, stk_n, stk_lost, ++stk_t, mut_p);
+      if (moved) {
+        const int np = mut_p + q - 1;
+        if (e_pos == mut_p) e_pos = np;
+        else if (e_pos > mut_p && e_pos <= np) e_pos -= 1;
+        if (C > mut_p && C <= np) C -= 1;
+      }
+    }
+    if (U(S->qw_rc[e]) != rc) {
+      stop = OS_STOP_CLASS;
+      break;
+    }
+    const int e_sl = __builtin_amdgcn_readlane(qw_sl, e);
+    const uint64_t tol = U64(S->qw_tol[e]);
+    const int Ce = __builtin_amdgcn_readlane(C, e);
+    const int32_t mem = O->memo[kl][e];
+    const bool rej = !((tol >> (e_ts & 63)) & 1) || mem == NC_NEVER || mem == e_ver ||
+                     !((e_r0 >= pr0) & (e_r1 >= pr1) & (e_r2 >= pr2) & (e_r3 >= pr3));
+    const uint64_t candm = __ballot(lane < n && e_pos <= Ce && !rej);
+    if (!candm) {  // the first-fit scan reaches a NodeClaim outside the set
+      stop = OS_STOP_NONOPEN;
+      break;
+    }
+    int w = 0, wp = INT32_MAX;
+    for (uint64_t m = candm; m; m &= m - 1) {
+      const int l = __builtin_ctzll(m);
+      const int p = __builtin_amdgcn_readlane(e_pos, l);
+      if (p < wp) wp = p, w = l;
+    }
+    if (__builtin_amdgcn_readlane(mem, w) < NC_MERGED) {  // a full NodeClaim.Add would run
+      stop = OS_STOP_UNKNOWN;
+      break;
+    }
+    // NodeClaim.Add on the append path: Fits over the remaining types
+    const int rl = min(lane, KP_NRES - 1);
+    const int64_t q_r = O->q[w][rl];
+    const int32_t j_r = O->fj[w][rl];
+    const uint64_t X0 = O->X[w][lane];
+    const int64_t q_lane = (lane < KP_NRES ? q_r : 0) + preq_lane;
+    const int32_t j0_lane = lane < KP_NRES ? j_r : 0;
+    const NbUnits fnb0 = fnb;
+    const uint64_t X = fits_lean(D, (const CatHdr LDS*)&g_hdr[0], X0, q_lane, j0_lane, (const int64_t LDS*)g_fitv, rrp,
+                                 n_rrp, fnb, (int32_t LDS*)fl_fitj);
+    if (UNLIKELY(!__ballot(X != 0))) {  // a rejection: the pod loop stores it and goes on with this pod
+      fnb = fnb0;
+      stop = OS_STOP_XZERO;
+      break;
+    }
+    const int32_t fj_r = fl_fitj[rl];
+    const int32_t fj = lane < KP_NRES ? fj_r : 0;
+    const bool xch = __ballot(lane < TW && X != X0) != 0, jch = __ballot(lane < KP_NRES && fj != j0_lane) != 0;
+    if (lane < KP_NRES) O->q[w][lane] = q_lane;
+    if (xch) O->X[w][lane] = X;
+    if (jch && lane < KP_NRES) O->fj[w][lane] = fj;
+    if (lane == w) {
+      e_r0 -= pr0, e_r1 -= pr1;
+      if (four) e_r2 -= pr2, e_r3 -= pr3;
+      e_ver += 1;
+      e_last = clock + 1;
+      e_dirty |= 1 | (xch ? 2 : 0) | (jch ? 4 : 0);
+    }
+    clock += 1;
+    const int ncw = __builtin_amdgcn_readlane(e_nc, w);
+    n_same += ncw == prev_nc;
+    prev_nc = ncw;
+    {  // len(Pods) + 1; the level's cursor; the placement (uniform values: every lane stores)
+      const int cnt1 = npods[ncw] + 1;
+      npods[ncw] = cnt1;
+      *reinterpret_cast<int2*>(&cur_nc[2 * e_sl]) = make_int2(wp, stk_t);
+      O->out_pod[k] = __builtin_amdgcn_readlane(qw_pod, e);
+      O->out_nc[k] = ncw;
+    }
+    mut = 1;
+    mut_p = wp;
+    k++;
+    wave_sync();
+  }
+
+  // every changed NodeClaim back to global memory, with the stores the pod loop's commit makes
+  for (int j = 0; j < OS_K; j++) {
+    const int d = j < n ? __builtin_amdgcn_readlane(e_dirty, j) : 0;
+    if (!d) continue;
+    const int ncj = __builtin_amdgcn_readlane(e_nc, j);
+    if (lane < KP_NRES) ((int64_t GLB*)A->nc_requests)[(size_t)ncj * KP_NRES + lane] = O->q[j][lane];
+    if ((d & 2) && lane < TW) ((uint64_t GLB*)A->nc_X)[(size_t)ncj * TW + lane] = O->X[j][lane];
+    if ((d & 4) && lane < KP_NRES) ((int32_t GLB*)A->nc_fitj)[(size_t)ncj * KP_NRES + lane] = O->fj[j][lane];
+    if (lane == j) {
+      NcHead* h = A->nc_head + ncj;
+      int4* hp = reinterpret_cast<int4*>(h);
+      hp[0] = make_int4((int)e_r0, (int)(e_r0 >> 32), (int)e_r1, (int)(e_r1 >> 32));
+      if (four) hp[1] = make_int4((int)e_r2, (int)(e_r2 >> 32), (int)e_r3, (int)(e_r3 >> 32));
+      h->ver = e_ver;
+    }
+  }
+  // the set survives when no mutation is pending (the next pod-loop iteration then replays none)
+  const bool valid = mut == 0;
+  if (lane < OS_K) {
+    O->nc[lane] = e_nc, O->pos[lane] = e_pos, O->ver[lane] = e_ver, O->ts[lane] = e_ts, O->last[lane] = e_last;
+    O->r[0][lane] = e_r0, O->r[1][lane] = e_r1, O->r[2][lane] = e_r2, O->r[3][lane] = e_r3;
+  }
+  O->cur[lane] = C;
+  if (lane == 0) {
+    O->n = valid ? n : 0;
+    O->pops = pops + k;
+    O->att = att + k;
+    O->win = qw_head;
+    O->clock = clock;
+    O->ret[0] = mut, O->ret[1] = mut_p, O->ret[2] = stk_n, O->ret[3] = stk_t, O->ret[4] = stk_lost;
+    O->ret[5] = n_same;
+    O->nb[0] += fnb.probes, O->nb[1] += fnb.rows, O->nb[2] += fnb.lb8;
+    if (OS_DIAG) O->stops[stop] += 1;
+  }
+  wave_sync();
+  return k;
+}
+
 // Places popped pods while they need no requirement merge; returns the number placed. A pod it cannot place is
 // handed to the full path through g_ctl[6] / g_ctl[26]. Called by wave 0 only. CHK: the order is chunked (the
 // directory in s_dyn, see chk_sort): the replay edits the blocks and the scan walks the live chunks, one per round.
 // EX: the Solve has existing nodes (addToExistingNode on the wave); without, that code is compiled out, so it costs
 // the Solves without existing nodes no registers (measured: 9 % of config 2's kernel when only skipped at run time).
 // CONT: 0 none; 1 the continuation round and the run-length commit; 2 the run-length commit alone (on config 2 the
-// round costs 3 % of the kernel and saves nothing once the commit takes the runs: 181.6 against 175.9 ms, measured).
+// round costs 3 % of the kernel and saves nothing once the commit takes the runs: 181.6 against 175.9 ms, measured);
+// 3 as 2 with the open set's loop (fl_open_set) in place of the closed-form commit (config 2: 161.1 -> 134.2 ms).
 template <bool TOPO, bool CHK, bool EX, int CONT>
 __device__ __noinline__ int fast_lane(uint64_t kargs, int32_t LDS* s_dyn_arg, uint64_t pops_in_arg) {
   // a callee's arguments arrive in VGPRs and count as divergent: made provably uniform here, or every value and
@@ -2333,6 +2629,12 @@ __device__ __noinline__ int fast_lane(uint64_t kargs, int32_t LDS* s_dyn_arg, ui
   // the loop)
   NbUnits fnb{0, 0, 0};
   uint32_t n_app = 0, n_scan = 0, n_run = 0;
+  if (CONT == 3) {  // the open set starts empty: another wave may have written NodeClaims since the last call
+    g_os.n = 0;  // (every lane stores)
+    g_os.pops = -2;
+    g_os.nb[0] = g_os.nb[1] = g_os.nb[2] = 0;
+    wave_sync();
+  }
     const bool tmg = A->timing != 0;
     // the argument block as a lane table: dword 64 k + l of SolveArgs in lane l of kt<k>
     static_assert(sizeof(SolveArgs) <= 1280, "SolveArgs outgrew the fast lane's argument table");
@@ -3248,7 +3550,61 @@ if (!FL_NOTIME && tmg) {                                    \
       //    a level's later occurrences read the cursor (wpos, now) its first one stored, which passes.
       // Each accepted entry's level gets the cursor (wpos, stk_t) the loop would have stored for it (the stamps of
       // the earlier ones differ from the loop's by pushes at wpos alone, which no query can tell apart).
-      if (CONT && cont_w == wpos && c_cat == 0 && c_hm == 0 && rr_b4p == 0 && n_rrp <= 4) {
+      //
+      // CONT 3: the open set's sequential loop in place of the closed form (fl_open_set): the following entries one at
+      // a time onto the last OS_K NodeClaims committed to, across threshold changes and sort.Slice moves.
+      if (CONT == 3 && cont_w == wpos && c_cat == 0 && c_hm == 0 && rr_b4p == 0 && n_rrp <= 4 && off + 1 < qw_n) {
+        OpenSet LDS* O = (OpenSet LDS*)&g_os;
+        {  // the call's uniform arguments through LDS (every lane stores)
+          O->arg[0] = off, O->arg[1] = qw_n, O->arg[2] = qw_head, O->arg[3] = epoch, O->arg[4] = q_len;
+          O->arg[5] = n_nc_all, O->arg[6] = wpos, O->arg[7] = placed, O->arg[8] = sl, O->arg[9] = c_ts;
+          O->arg[10] = c_ver, O->arg[11] = stk_n, O->arg[12] = stk_t, O->arg[13] = stk_lost, O->arg[14] = pops;
+          O->arg[15] = (int)(uint32_t)attempts;
+          O->arg_r[0] = c_r0, O->arg_r[1] = c_r1, O->arg_r[2] = c_r2, O->arg_r[3] = c_r3;
+        }
+        wave_sync();
+        const int k = U(fl_open_set(((uint64_t)khi << 32) | klo, s_dyn, c_X, c_q, c_fj, preq_lane, qw_pod, qw_sl, qw_epoch,
+                                    qw_lastlen));
+        mut = U(O->ret[0]), mut_p = U(O->ret[1]), stk_n = U(O->ret[2]), stk_t = U(O->ret[3]), stk_lost = U(O->ret[4]);
+        if (k > 0) {
+          c_nc = -1;  // (the set wrote its NodeClaims back: the next pod reads them)
+          cont_w = -1;
+          prev_sl = -1;
+          if (n_buf + k > 64) {
+            if (lane < n_buf) {
+              KA(placement)[buf_pod] = buf_pl;
+              KA(events)[n_ev + lane] = buf_pod;
+            }
+            n_ev += n_buf;
+            n_buf = 0;
+          }
+          const int bi = (lane - n_buf) & 63;
+          const int bp = O->out_pod[bi], bn = O->out_nc[bi];
+          if (lane >= n_buf && lane < n_buf + k) {
+            buf_pod = bp;
+            buf_pl = bn;
+          }
+          n_buf += k;
+          if (n_buf == 64) {
+            KA(placement)[buf_pod] = buf_pl;
+            KA(events)[n_ev + lane] = buf_pod;
+            n_ev += 64;
+            n_buf = 0;
+          }
+          q_head += k;
+          if (q_head >= KA(n_pods)) q_head -= KA(n_pods);
+          q_len -= k;
+          qw_next = off + 1 + k;
+          pf_off = -1;
+          pops += k;
+          attempts += k;
+          n_app += (uint32_t)k;
+          n_scan += (uint32_t)k;
+          // (those on the NodeClaim of the pod before them: run_length_pods; an OS_DIAG build counts the loop's reach)
+          n_run += OS_DIAG ? (uint32_t)k : (uint32_t)U(O->ret[5]);
+        }
+      }
+      if (CONT && CONT != 3 && cont_w == wpos && c_cat == 0 && c_hm == 0 && rr_b4p == 0 && n_rrp <= 4) {
         const int e = off + 1 + lane;  // lane j: the j-th window entry after this pod
         const int e_sl = __shfl(qw_sl, e & 63, 64), e_ep = __shfl(qw_epoch, e & 63, 64),
                   e_ll = __shfl(qw_lastlen, e & 63, 64), e_pod = __shfl(qw_pod, e & 63, 64);
@@ -3388,6 +3744,7 @@ if (!FL_NOTIME && tmg) {                                    \
     S->qw_head = qw_head;
     S->qw_n = qw_n;
     S->qw_next = qw_next;
+    if (CONT == 3) fnb.probes += g_os.nb[0], fnb.rows += g_os.nb[1], fnb.lb8 += g_os.nb[2];  // fl_open_set's Fits
     bytes += (uint64_t)fnb.probes * 512 + (uint64_t)fnb.rows * D.TW * 8 + (uint64_t)fnb.lb8 * 8 +
              (uint64_t)n_app * ((uint64_t)D.TW * 8 + KP_NRES * 8 + 8) + (uint64_t)n_scan * (12 + 16 * A->n_req_res);
     S->bytes += bytes;
@@ -3534,6 +3891,8 @@ __global__ __launch_bounds__(NW * 64) void solve_kernel(SolveArgs a0, const Solv
     for (int i = 0; i < 8; i++) g_fast.fbail[i] = 0;
     if (SORT_DIAG || EX_DIAG || FX_DIAG || MERGE_DIAG)
       for (int i = 0; i < 6; i++) g_sdiag[i] = 0;
+    if (OS_DIAG)
+      for (int i = 0; i < OS_STOP_N; i++) g_os.stops[i] = 0;
     g_rqc = RqcTab{a.nc_fail, a.sl_rqc, a.rqc_off, a.rqc_mem, a.ncc, a.rqc_empty};
   }
   __syncthreads();
@@ -3566,6 +3925,8 @@ __global__ __launch_bounds__(NW * 64) void solve_kernel(SolveArgs a0, const Solv
                                      : fast_lane<TOPO, true, false, 0>(kargs, (int32_t LDS*)s_dyn, pops);
         else if (a.n_existing)
           placed_fast = fast_lane<TOPO, false, true, 0>(kargs, (int32_t LDS*)s_dyn, pops);
+        else if (!TOPO && a.cont == 3)  // (cont 3: cont 2 with the open set's loop in place of the closed form)
+          placed_fast = fast_lane<TOPO, false, false, TOPO ? 0 : 3>(kargs, (int32_t LDS*)s_dyn, pops);
         else if (!TOPO && a.cont == 2)
           placed_fast = fast_lane<TOPO, false, false, TOPO ? 0 : 2>(kargs, (int32_t LDS*)s_dyn, pops);
         else if (!TOPO && a.cont)
@@ -4435,6 +4796,8 @@ __global__ __launch_bounds__(NW * 64) void solve_kernel(SolveArgs a0, const Solv
       for (int i = 0; i < 8; i++) a.stats[16 + i] = g_fast.fcyc[6 + i];
     if (SORT_DIAG || EX_DIAG || FX_DIAG || MERGE_DIAG)
       for (int i = 0; i < 6; i++) a.stats[25 + i] = g_sdiag[i];
+    if (OS_DIAG)
+      for (int i = 0; i < OS_STOP_N; i++) a.stats[25 + i] = g_os.stops[i];
     // chunked order: peak chunks, splits, emptied chunks, (re)builds; final order mode
     a.stats[41] = g_chk.nch_peak;
     a.stats[42] = g_chk.splits;
@@ -4996,7 +5359,7 @@ __global__ __launch_bounds__(FEASB_WAVES * 64, FEASB_MINW) void feasibility_bits
 #define FEASQ_MINW 6  // waves per SIMD the quad kernel's register budget targets (8: 9 VGPRs spilled; 6: none, -4..6 %)
 #endif
 static_assert(KP_DIAG_BUILD || (FASTLANE == 1 && FL_NOTIME == 1 && FT_FINE == 0 && FAST_SCAN_MAX == 512 &&
-                                 FAST_CHK_LIVE == 8 && FAST_EX_ROUNDS == 8 && FAST_CONT == 1 && SORT_DIAG == 0 && EX_DIAG == 0 && FX_DIAG == 0 && REQ_CLASSES == 3 && MERGE_DIAG == 0 && FEAS_MAX_BLOCKS == 65536 &&
+                                 FAST_CHK_LIVE == 8 && FAST_EX_ROUNDS == 8 && FAST_CONT == 1 && SORT_DIAG == 0 && EX_DIAG == 0 && FX_DIAG == 0 && REQ_CLASSES == 3 && MERGE_DIAG == 0 && OS_DIAG == 0 && FEAS_MAX_BLOCKS == 65536 &&
                                  FEASQ_EW == 7 && FEASQ_ROWS == 28 && FEASQ_B128 == 1 && FEASQ_SKIP_EVAL == 0 && FL_SKIP == 0 &&
                                  FEASQ_MINW == 6),
               "the production build carries the production values of every measurement knob");

@@ -1,6 +1,6 @@
 """solve_kernel time of one config (default 2): 1 warmup + 5 timed kp_solve calls; prints the kernel ms (min, mean),
 the per-Solve prepare and the whole call (means).
-Works with any libkp build selected by KP_LIB (older ABIs included). usage: kernel_time.py [2|3|5] [pods]"""
+Works with any libkp build selected by KP_LIB (older ABIs included). usage: kernel_time.py [1|2|2b|3|5] [pods]"""
 import json
 import os
 import sys
@@ -17,10 +17,11 @@ if cfg.endswith("-off"):  # the fast lane without its continuation variant (kp_s
 elif cfg.endswith("-on"):  # the fast lane with its continuation variant
     os.environ["KP_CONT"] = "1"
     cfg = cfg[:-3]
-n = int(sys.argv[2]) if len(sys.argv) > 2 else {"2": 50000, "2b": 50000, "3": 100000, "5": 100000}[cfg]
+n = int(sys.argv[2]) if len(sys.argv) > 2 else {"1": 1000, "2": 50000, "2b": 50000, "3": 100000, "5": 100000}[cfg]
 lib = kpamd.load_lib()
 cat = catalog.build_catalog(lib)
-prob = {"2": lambda: synth.config2(cat, n_pods=n, seed=2), "2b": lambda: synth.config2(cat, n_pods=n, seed=2, burst=True),
+prob = {"1": lambda: synth.config1(cat, n_pods=n, seed=1),
+        "2": lambda: synth.config2(cat, n_pods=n, seed=2), "2b": lambda: synth.config2(cat, n_pods=n, seed=2, burst=True),
         "3": lambda: synth.config3(cat, n_pods=n), "5": lambda: synth.config5(cat, n_pods=n)}[cfg]()
 ctx = kpamd.Context(0)
 import _ov  # noqa: E402  (tools only: diagnostic variables -> kp_overrides)

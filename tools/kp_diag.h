@@ -22,6 +22,10 @@
  *                        requirement classes)
  *   MERGE_DIAG [0]       with FT_FINE: the fast lane's attempt interval FTF(11) by kind in stats[25..30]: merges, failed
  *                        full adds, appends (count, cycles each); KP_TIMING=1 MERGE_DIAG=1 tools/profile_solve.py
+ *   OS_DIAG [0]          the open-set loop's stops by reason in stats[25..30]: another class, untagged level, NodeClaim
+ *                        outside the set, Fits empties the types, literal pdqsort, window end / Queue.Pop stop; and
+ *                        run_length_pods counts every pod the loop placed (its reach), not only those on the NodeClaim
+ *                        of the pod before them
  *   FEAS_MAX_BLOCKS [65536], FEASQ_EW [7], FEASQ_ROWS [28], FEASQ_B128 [1]  feasibility grid / block shape
  *   FEASQ_SKIP_EVAL [0]  decode + copies only, no type-set work: WRONG MASKS, timing experiments only
  *   FEASQ_MINW [6]       feasibility_quad_kernel register budget (waves per SIMD)
