@@ -145,7 +145,9 @@ typedef struct kp_offering {
   const char* zone_id;       /* topology.k8s.aws/zone-id In {zone_id}; NULL: no zone-id requirement */
   const char* reservation_id;   /* capacity-reservation-id In {id}; NULL: DoesNotExist (R:offering.go:136) */
   const char* reservation_type; /* capacity-reservation-type In {type}; NULL: DoesNotExist (R:offering.go:137) */
-  double price;
+  double price;              /* a number >= 0 (+inf allowed): a negative or NaN price is refused with KP_E_INVAL by
+                                kp_catalog_upload and kp_catalog_update_offerings, -0.0 is stored as +0.0. The device
+                                orders prices by their bit patterns, which equals < on this domain only. */
   int32_t available;
   int32_t reservation_capacity; /* Offering.ReservationCapacity (R:offering.go:178): read by ReservedOfferingFilter.
                                    Filter and launch plans take reserved offerings (ABI v7), Solve plans too (ABI
@@ -489,7 +491,7 @@ typedef struct kp_offering_update {
   int32_t available;          /* 0: ICE / unavailable, 1: available */
   const char* capacity_type;
   const char* zone;
-  double price;               /* NaN: keep */
+  double price;               /* NaN: keep (so a NaN price cannot be set); else kp_offering.price's domain */
   /* ABI v7: capacity reservations (capacityreservation.Provider.MarkUnavailable / GetAvailableInstanceCount,
    * R:pkg/providers/instance/instance.go:470-484): a non-NULL reservation_id narrows the match to that
    * reservation's offerings; reservation_capacity >= 0 sets ReservationCapacity (-1: keep). */

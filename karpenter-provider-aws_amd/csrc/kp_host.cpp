@@ -959,6 +959,14 @@ int32_t kp_ctx_get_overrides(const kp_ctx* ctx, kp_overrides* out) {
 int32_t kp_catalog_upload(kp_ctx* ctx, const kp_catalog_desc* desc, uint64_t seqnum, kp_catalog** out) {
   if (!desc || !out) return fail(KP_E_INVAL, "null argument");  // ctx NULL: host-only (kp_solve_validate)
   if (desc->n_types > 4096) return fail(KP_E_UNSUPPORTED, "%u instance types (max 4096)", desc->n_types);
+  // the price domain (kp_abi.h): the device orders prices by their bit patterns, which holds for p >= +0.0 only
+  for (uint32_t i = 0; i < desc->n_types; i++)
+    for (uint32_t j = 0; j < desc->types[i].n_offerings; j++) {
+      const double p = desc->types[i].offerings[j].price;
+      if (std::isnan(p) || p < 0)
+        return fail(KP_E_INVAL, "type %u (%s): offering %u has price %g (a price is a number >= 0)", i,
+                    desc->types[i].name ? desc->types[i].name : "", j, p);
+    }
   static std::atomic<uint64_t> next_uid{1};
   auto* c = new kp_catalog();
   c->ctx = ctx;
@@ -977,7 +985,7 @@ int32_t kp_catalog_upload(kp_ctx* ctx, const kp_catalog_desc* desc, uint64_t seq
     for (uint32_t j = 0; j < t.n_offerings; j++) {
       const kp_offering& o = t.offerings[j];
       h.offs.push_back({o.capacity_type ? o.capacity_type : "", o.zone ? o.zone : "", o.zone_id ? o.zone_id : "",
-                        o.zone != nullptr, o.zone_id != nullptr, o.price, o.available != 0});
+                        o.zone != nullptr, o.zone_id != nullptr, o.price + 0.0, o.available != 0});  // (-0.0 -> +0.0)
       HostOffering& ho = h.offs.back();
       ho.has_rid = o.reservation_id != nullptr;
       ho.has_rt = o.reservation_type != nullptr;
@@ -1026,6 +1034,9 @@ int32_t kp_catalog_update_offerings(kp_catalog* c, const kp_offering_update* ups
   for (uint32_t i = 0; i < n; i++) {
     if (ups[i].type >= c->types.size())
       return fail(KP_E_INVAL, "update %u: type %u of %zu", i, ups[i].type, c->types.size());
+    if (ups[i].price < 0)  // (NaN: keep; the price domain of kp_abi.h otherwise)
+      return fail(KP_E_INVAL, "update %u: type %u (%s) given price %g (a price is a number >= 0)", i, ups[i].type,
+                  c->types[ups[i].type].name.c_str(), ups[i].price);
     bool any = false;
     for (auto& o : c->types[ups[i].type].offs) {
       if (!match(o, ups[i])) continue;
@@ -1042,7 +1053,7 @@ int32_t kp_catalog_update_offerings(kp_catalog* c, const kp_offering_update* ups
     for (auto& o : c->types[ups[i].type].offs)
       if (match(o, ups[i])) {
         o.available = ups[i].available != 0;
-        if (!std::isnan(ups[i].price)) o.price = ups[i].price;
+        if (!std::isnan(ups[i].price)) o.price = ups[i].price + 0.0;  // (-0.0 -> +0.0)
         if (ups[i].reservation_capacity >= 0) o.rcap = ups[i].reservation_capacity;
       }
   c->seqnum = seqnum;

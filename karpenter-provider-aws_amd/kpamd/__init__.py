@@ -198,6 +198,10 @@ class Catalog:
         device-side catalogue (all or nothing)."""
         def opt(u, i):
             return u[i] if len(u) > i else None
+        for i, u in enumerate(updates):  # (behind the ABI a NaN price means "keep": it cannot be set)
+            if opt(u, 4) is not None and float(u[4]) != float(u[4]):
+                raise KPError(abi.KP_E_INVAL, f"update {i}: type {u[0]} ({self.instance_types[u[0]].name}) given price "
+                                              f"nan (a price is a number >= 0)")
         ups = [abi.OfferingUpdate(int(u[0]), 1 if u[3] else 0, u[1].encode() if u[1] is not None else None,
                                   u[2].encode() if u[2] is not None else None,
                                   float(u[4]) if opt(u, 4) is not None else float("nan"),
@@ -210,7 +214,7 @@ class Catalog:
                 if o.capacity_type == u[1] and o.zone == u[2] and (opt(u, 5) is None or o.reservation_id == opt(u, 5)):
                     o.available = bool(u[3])
                     if opt(u, 4) is not None:
-                        o.price = float(u[4])
+                        o.price = float(u[4]) + 0.0  # (-0.0 is stored as +0.0)
                     if opt(u, 6) is not None and int(opt(u, 6)) >= 0:
                         o.reservation_capacity = int(opt(u, 6))
 

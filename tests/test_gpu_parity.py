@@ -2,6 +2,10 @@
 
 Compared: every pod's placement (NodeClaim creation index / existing node / error) and every NodeClaim's
 NodePool, pod list in add order, and instance-type options after OrderByPrice + Truncate(100).
+
+The option lists here are a by-product of placement parity on the real price table, where ties are rare and the list
+lengths are whatever the workload leaves. tests/test_option_order.py aims at that step itself: price ties at the cut,
+all-equal lists, prices one ulp apart, list lengths at the kernels' size boundaries, max_instance_types 0, 1 and 101.
 """
 import numpy as np
 import pytest
