@@ -759,6 +759,58 @@ int32_t kp_result_nodeclaim(const kp_solve_result* res, uint32_t i, kp_nodeclaim
 int32_t kp_result_stats(const kp_solve_result* res, kp_solve_stats* out);
 void kp_result_destroy(kp_solve_result* res);
 
+/* ---- Why a pod is unschedulable (entry points added under ABI v13) ------------------------------
+ * Upstream Scheduler.add returns, for a pod it cannot place, one error per NodeClaimTemplate ("incompatible with
+ * nodepool ..."); the controller publishes them as the pod's FailedScheduling event. An explained Solve returns their
+ * causes: for every pod it left unscheduled (placement -1), one kp_pool_reason per template, in the Solve's template
+ * order (weight descending, name ascending; NodePools whose own requirements leave no instance type have no template
+ * and no entry). An entry is what addToNewNodeClaim reports at the state the Solve ENDED in: the pod at its final
+ * relaxation level, the remaining limits and topology counts as the Solve left them, a fresh NodeClaim. (The queue
+ * stops only after a full cycle without a placement, so every failed pod's last attempt ran against that state; the
+ * one exception is a topology group another pod's later relaxation made live, see DESIGN.) Errors from existing nodes
+ * and in-flight NodeClaims are discarded, as upstream discards them.
+ * Per template the first cause that holds is `code`, in the order of enum kp_why. The library returns no message
+ * strings beyond the label keys: the shim builds the text.
+ * Not covered (KP_E_UNSUPPORTED from the explained entry points): Solves over capacity reservations (a
+ * ReservedOfferingError depends on reservation capacities that do not outlive the Solve). The cluster plans and the
+ * general consolidation path have no explained form. */
+enum kp_why {
+  KP_WHY_NONE = 0,           /* the attempt would succeed at the final state (legal; see above) */
+  KP_WHY_LIMITS = 1,         /* the NodePool has limits and filterByRemainingResources leaves no option */
+  KP_WHY_TAINT = 2,          /* the final level's tolerations do not tolerate the template's taints */
+  KP_WHY_REQUIREMENTS = 3,   /* Compatible(template requirements, pod requirements, allow undefined well-known) fails */
+  KP_WHY_TOPOLOGY = 4,       /* Topology.AddRequirements, its Compatible with the merged requirements, or the pod-affinity
+                                bootstrap rule of a fresh NodeClaim fails */
+  KP_WHY_INSTANCE_TYPES = 5, /* filterInstanceTypesByRequirements: no option passes all three criteria */
+  KP_WHY_MIN_VALUES = 6      /* n_remaining options pass them, but the set breaks a minValues requirement */
+};
+typedef struct kp_pool_reason {
+  uint32_t nodepool;            /* index into kp_solve_in.nodepools */
+  int32_t code;                 /* enum kp_why */
+  int32_t taint;                /* KP_WHY_TAINT: index in the NodePool's taints of the first one not tolerated; else -1 */
+  uint32_t n_types;             /* the template's options after the limits (filled from KP_WHY_TAINT on; 0 for LIMITS) */
+  /* KP_WHY_INSTANCE_TYPES / KP_WHY_MIN_VALUES (0 otherwise): of those n_types options, how many pass each criterion of
+   * filterInstanceTypesByRequirements on its own, against the merged requirements and daemon + pod requests:
+   * Intersects(type, merged); Fits(total, allocatable); some available offering Compatible with merged. Upstream's
+   * six booleans (requirementsMet, fits, hasOffering and their pairs) are these counts compared with 0. */
+  uint32_t n_requirements, n_fits, n_offering;
+  uint32_t n_requirements_fits, n_requirements_offering, n_fits_offering;
+  uint32_t n_remaining;         /* options passing all three (> 0 exactly for KP_WHY_MIN_VALUES) */
+  uint32_t n_keys;              /* KP_WHY_REQUIREMENTS: the label keys Compatible fails on ... */
+  const char* const* keys;      /* ... in byte order; owned by the result */
+} kp_pool_reason;
+/* kp_solve_cancellable / kp_solve_run_cancellable (cancel may be NULL) with the explanation step behind the Solve, on
+ * the same stream, before the copy-back: same placements, NodeClaims and stats. kp_solve / kp_solve_run never run it. */
+int32_t kp_solve_explained(kp_ctx* ctx, const kp_solve_in* in, kp_cancel* cancel, kp_solve_result** out);
+int32_t kp_solve_run_explained(kp_solve_plan* plan, kp_cancel* cancel, kp_solve_result** out);
+/* 1: the result came from an explained entry point */
+int32_t kp_result_explained(const kp_solve_result* res);
+/* entries kp_result_pod_reasons has for `pod`: the template count for an unscheduled pod of an explained result, else 0
+ * (a pod that lost its NodeClaim to Truncate's minValues check on the host was placed by the Solve and has none) */
+uint32_t kp_result_reason_count(const kp_solve_result* res, uint32_t pod);
+/* writes min(n, count) entries. KP_E_INVAL: pod out of range, or the result was not explained */
+int32_t kp_result_pod_reasons(const kp_solve_result* res, uint32_t pod, kp_pool_reason* out, uint32_t n);
+
 /* ---- Disruption: batched consolidation simulations ---------------------------------------------
  * Cluster snapshot as the disruption controller sees it (state.Cluster nodes + their reschedulable pods),
  * and a batch of candidate subsets. For each subset S, kp_simulate_batch computes what upstream

@@ -234,6 +234,61 @@ struct TfeasArgs {
 };
 hipError_t launch_tmpl_feas(const TfeasArgs& a, hipStream_t s);
 
+// The explanation step behind a Solve (kp_solve_run_explained): why addToNewNodeClaim fails, per NodePool template, for
+// the shape-levels the Solve left pods of unscheduled, at the state solve_kernel ended in. One record per (shape-level,
+// template); mirrors kp_pool_reason's numeric half (codes: enum kp_why).
+struct ExplainRec {
+  int32_t code;
+  int32_t n_types;      // the template's options after filterByRemainingResources
+  int32_t n_req, n_fits, n_off;  // options passing one criterion alone: Intersects / Fits / an available offering
+  int32_t n_rf, n_ro, n_fo;      // ... each pair
+  int32_t n_remaining;  // ... all three
+  int32_t pad_;
+  uint64_t keys;        // KP_WHY_REQUIREMENTS: the dictionary keys Compatible fails on
+};
+struct ExplainArgs {
+  const DevDict* dict;
+  const DevCatalog* cats;
+  int32_t n_catalogs;
+  const int64_t* vint;
+  // the Solve's final state (read only)
+  int32_t n_pods;
+  const int32_t* pod_shape;          // [P]
+  const int32_t* pod_level;          // [P]
+  const int32_t* placement;          // [P]
+  const int64_t* tmpl_remaining;     // [NT][NRES]
+  const int32_t* tg_cnt;             // [G][64]
+  const uint64_t* tg_reg;            // [G]
+  // the batch (as SolveArgs / TfeasArgs)
+  int32_t n_sl, n_tmpl;
+  const int32_t* shape_level_base;   // [S]
+  const int32_t* sl_shape;           // [SL]
+  const uint8_t* shape_reqs;         // [SL] KReqs
+  const uint64_t* shape_negop;       // [SL]
+  const uint64_t* shape_tolerates;   // [SL]
+  const int64_t* shape_requests;     // [S][NRES]
+  const uint64_t* shape_pvp;
+  const int32_t* pvp_base;
+  const int32_t* pvp_slot;
+  const uint8_t* tmpl_reqs;
+  const int32_t* tmpl_taintset;
+  const int32_t* tmpl_catalog;
+  const uint64_t* tmpl_X;
+  const int64_t* tmpl_daemon;
+  const uint32_t* tmpl_limit_present;
+  const int32_t* sl_own_base;        // [SL]
+  const int32_t* sl_own_n;           // [SL] (<= 8)
+  const int4* own_rec;
+  const uint64_t* own_pd;
+  const uint64_t* sl_topo_keys;      // [SL]
+  uint32_t req_res_mask;
+  // outputs: the only words the two kernels write
+  uint8_t* mark;                     // [SL] 1: some unscheduled pod ended at this shape-level (zeroed before the launch)
+  int32_t* pod_row;                  // [P] the pod's shape-level when it is unscheduled, else -1
+  ExplainRec* rec;                   // [SL][NT], rows of marked shape-levels only
+};
+hipError_t launch_explain(const ExplainArgs& a, hipStream_t s);
+
 struct FinalizeArgs {
   const DevDict* dict;
   const DevCatalog* cats;

@@ -912,6 +912,17 @@ struct kp_solve_result {
   kp_solve_stats stats;
   vector<KReqs> fin;     // per NodeClaim: final requirements (device encoding), for in-library callers
   vector<int> nc_cat;    // per NodeClaim: catalogue of its template
+  // explained results (kp_solve_run_explained): one record per (shape-level row, template); pod_row[p] = the row of an
+  // unscheduled pod, else -1. why_keys[row * n_tmpl + t]: the failing label keys of a KP_WHY_REQUIREMENTS record,
+  // pointers into key_names (the result's own copy of the dictionary's key strings)
+  bool explained = false;
+  int n_tmpl = 0;
+  vector<int32_t> pod_row;
+  vector<ExplainRec> why;
+  vector<int32_t> why_taint;             // [rows][n_tmpl] first untolerated taint of the NodePool, -1: tolerated
+  vector<uint32_t> why_nodepool;         // [n_tmpl]
+  vector<string> key_names;
+  std::unordered_map<size_t, vector<const char*>> why_keys;
 };
 
 extern "C" {
@@ -3598,6 +3609,40 @@ void CommReadSettings(kp_comm* c) {
   c->tfeas_shard_min = 1u << 20;
   if (c->ctx->ov.table_shard_min) c->tfeas_shard_min = c->ctx->ov.table_shard_min;
 }
+
+// Per (shape-level, template) whose taints the level does not tolerate (shape_tolerates): the index, in the NodePool's
+// own taints order, of the first taint no toleration of the level matches (Taints.ToleratesPod reports the first);
+// -1 where every taint is tolerated.
+vector<int32_t> TaintFirst(const kp_solve_in* in, const Compiled& C) {
+  const SolveBase& b = *C.B;
+  const size_t NT = b.tmpl_nodepool.size(), SL = C.shape_reqs.size();
+  vector<int32_t> out(std::max<size_t>(SL * NT, 1), -1);
+  for (size_t s = 0; s < C.shape_level_base.size(); s++) {
+    const kp_pod_shape& sh = in->shapes[s];
+    for (int l = 0; l < C.shape_nlevels[s]; l++) {
+      const size_t sl = (size_t)C.shape_level_base[s] + l;
+      const bool pns = C.sl_pns[sl] != 0;
+      for (size_t t = 0; t < NT; t++) {
+        if ((C.shape_tolerates[sl] >> b.tmpl_taintset[t]) & 1) continue;
+        const kp_nodepool& np = in->nodepools[b.tmpl_nodepool[t]];
+        for (uint32_t i = 0; i < np.n_taints && out[sl * NT + t] < 0; i++) {
+          const string xk = np.taints[i].key ? np.taints[i].key : "", xv = np.taints[i].value ? np.taints[i].value : "";
+          bool ok = false;
+          for (uint32_t j = 0; j < sh.n_tolerations + (pns ? 1 : 0) && !ok; j++) {
+            const kp_toleration& tl = j < sh.n_tolerations ? sh.tolerations[j] : kPnsToleration;
+            const string tk = tl.key ? tl.key : "", tv = tl.value ? tl.value : "";
+            if (tl.effect != KP_EFFECT_ANY && tl.effect != np.taints[i].effect) continue;
+            if (!tk.empty() && tk != xk) continue;
+            if (tl.op == KP_TOL_EQUAL) ok = tv == xv;
+            else if (tl.op == KP_TOL_EXISTS) ok = true;
+          }
+          if (!ok) out[sl * NT + t] = (int32_t)i;
+        }
+      }
+    }
+  }
+  return out;
+}
 }  // namespace
 
 struct kp_solve_plan {
@@ -3617,6 +3662,12 @@ struct kp_solve_plan {
   uint64_t base_version = 0;  // SolveBase::version the plan's derived data (template-options table) reflects
   TfeasArgs tf;               // the table's launch over every row (kp_solve_refresh recomputes it locally)
   bool tfeas_on = false;
+  // the explanation step (kp_solve_run_explained): its launch, the arena block it writes (records, then the per-pod row
+  // index: one download) and the mark table behind it; per (shape-level, template) the index in the NodePool's taints
+  // of the first taint the level does not tolerate (-1: all tolerated)
+  ExplainArgs ex;
+  size_t o_why = 0, n_why = 0, o_mark = 0, n_mark = 0;
+  vector<int32_t> taint_first;
 };
 
 extern "C" {
@@ -3746,6 +3797,13 @@ static int32_t SolvePrepareLocal(kp_ctx* ctx, const kp_solve_in* in, kp_comm* co
   const int rows_per_rank = (SLi + n_ranks - 1) / n_ranks;
   const size_t tf_bytes = tfeas_on ? (size_t)rows_per_rank * n_ranks * NT * tf_words * sizeof(uint64_t) : 0;
   o.tfeas = blob.reserve_dev(std::max<size_t>(tf_bytes, 8));
+  // the explanation step's outputs: records [SL][NT] and the per-pod row index in one block, then the mark table
+  const size_t SLx = std::max(SLi, 1), NTx = std::max(NT, 1);
+  const size_t why_rec_bytes = sizeof(ExplainRec) * SLx * NTx;
+  plan->n_why = why_rec_bytes + sizeof(int32_t) * (size_t)Pc;
+  plan->o_why = blob.reserve_dev(plan->n_why);
+  plan->n_mark = SLx;
+  plan->o_mark = blob.reserve_dev(plan->n_mark);
   const size_t total_bytes = blob.total();
 
   // the per-Solve arena: reuse the ctx's spare allocation when it is large enough
@@ -3788,6 +3846,25 @@ static int32_t SolvePrepareLocal(kp_ctx* ctx, const kp_solve_in* in, kp_comm* co
     a.tfeas_words = tf_words;
   }
 
+  {
+    ExplainArgs& x = plan->ex;
+    memset(&x, 0, sizeof x);
+    x.dict = a.dict, x.cats = a.cats, x.n_catalogs = a.n_catalogs, x.vint = a.vint;
+    x.n_pods = P, x.pod_shape = a.pod_shape, x.pod_level = a.pod_level, x.placement = a.placement;
+    x.tmpl_remaining = a.tmpl_remaining, x.tg_cnt = a.tg_cnt, x.tg_reg = a.tg_reg;
+    x.n_sl = SLi, x.n_tmpl = NT;
+    x.shape_level_base = a.shape_level_base, x.sl_shape = (const int32_t*)(base + o.slsh);
+    x.shape_reqs = a.shape_reqs, x.shape_negop = a.shape_negop, x.shape_tolerates = a.shape_tolerates;
+    x.shape_requests = a.shape_requests, x.shape_pvp = a.shape_pvp, x.pvp_base = a.pvp_base, x.pvp_slot = a.pvp_slot;
+    x.tmpl_reqs = a.tmpl_reqs, x.tmpl_taintset = a.tmpl_taintset, x.tmpl_catalog = a.tmpl_catalog, x.tmpl_X = a.tmpl_X;
+    x.tmpl_daemon = a.tmpl_daemon, x.tmpl_limit_present = a.tmpl_limit_present;
+    x.sl_own_base = a.sl_own_base, x.sl_own_n = a.sl_own_n, x.own_rec = a.own_rec, x.own_pd = a.own_pd;
+    x.sl_topo_keys = a.sl_topo_keys, x.req_res_mask = a.req_res_mask;
+    x.rec = (ExplainRec*)(base + plan->o_why);
+    x.pod_row = (int32_t*)(base + plan->o_why + why_rec_bytes);
+    x.mark = base + plan->o_mark;
+    plan->taint_first = TaintFirst(in, C);
+  }
   plan->o_ver = o.ver0;
   plan->n_ver = o.ver_end - o.ver0;
   plan->o_fail = o.fail0;
@@ -4004,11 +4081,67 @@ static int32_t AssembleResult(const SolveBase& B, const uint64_t* stats, ArenaRe
 }
 
 // One Solve over resident inputs: restore mutable state, solve_kernel, finalize_kernel, copy results.
-int32_t kp_solve_run(kp_solve_plan* plan, kp_solve_result** out) { return kp_solve_run_cancellable(plan, nullptr, out); }
-
+static int32_t SolveRun(kp_solve_plan* plan, kp_cancel* cancel, bool explain, kp_solve_result** out);
+int32_t kp_solve_run(kp_solve_plan* plan, kp_solve_result** out) { return SolveRun(plan, nullptr, false, out); }
 int32_t kp_solve_run_cancellable(kp_solve_plan* plan, kp_cancel* cancel, kp_solve_result** out) {
+  return SolveRun(plan, cancel, false, out);
+}
+// The Solve, then the explanation step on the same stream before the copy-back: explain_mark_kernel + explain_kernel read
+// the state solve_kernel left (placements, levels, remaining limits, topology counts) and write their own block only
+int32_t kp_solve_run_explained(kp_solve_plan* plan, kp_cancel* cancel, kp_solve_result** out) {
+  return SolveRun(plan, cancel, true, out);
+}
+
+// The explained result's host half: the records and the per-pod rows in one download; the key masks of
+// KP_WHY_REQUIREMENTS records resolved to the dictionary's strings (byte order), the taint index from the plan's table
+static int32_t FetchReasons(kp_solve_plan* plan, hipStream_t st, kp_solve_result& res) {
+  const SolveBase& B = *plan->cp->B;
+  const Dict& d = B.d;
+  const size_t NT = B.tmpl_nodepool.size(), SL = plan->cp->shape_reqs.size();
+  const size_t n_rec = std::max<size_t>(SL, 1) * std::max<size_t>(NT, 1);
+  vector<uint8_t> blockv(plan->n_why);
+  HIPCHK(hipMemcpyAsync(blockv.data(), (uint8_t*)plan->buf.p + plan->o_why, plan->n_why, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  res.explained = true;
+  res.n_tmpl = (int)NT;
+  res.why.resize(n_rec);
+  memcpy(res.why.data(), blockv.data(), sizeof(ExplainRec) * n_rec);
+  res.pod_row.assign(plan->P, -1);
+  if (plan->P) memcpy(res.pod_row.data(), blockv.data() + sizeof(ExplainRec) * n_rec, sizeof(int32_t) * plan->P);
+  res.why_taint = plan->taint_first;
+  for (int np : B.tmpl_nodepool) res.why_nodepool.push_back((uint32_t)np);
+  res.key_names = d.keys;
+  vector<char> seen(std::max<size_t>(SL, 1), 0);
+  for (int p = 0; p < plan->P; p++) {
+    const int32_t row = res.pod_row[p];
+    if (row < 0) continue;
+    if ((size_t)row >= SL) return fail(KP_E_DEVICE, "explanation: pod %d names shape-level %d of %zu", p, row, SL);
+    if (seen[row]) continue;
+    seen[row] = 1;
+    for (size_t t = 0; t < NT; t++) {
+      const ExplainRec& r = res.why[(size_t)row * NT + t];
+      if (r.code < KP_WHY_NONE || r.code > KP_WHY_MIN_VALUES)
+        return fail(KP_E_DEVICE, "explanation: record (%d, %zu) holds code %d", row, t, r.code);
+      if (r.code != KP_WHY_REQUIREMENTS) continue;
+      vector<int> ks;
+      for (uint64_t m = r.keys; m; m &= m - 1) {
+        const int k = __builtin_ctzll(m);
+        if (k >= (int)res.key_names.size()) return fail(KP_E_DEVICE, "explanation: key %d of %zu", k, res.key_names.size());
+        ks.push_back(k);
+      }
+      std::sort(ks.begin(), ks.end(), [&](int x, int y) { return res.key_names[x] < res.key_names[y]; });
+      auto& v = res.why_keys[(size_t)row * NT + t];
+      for (int k : ks) v.push_back(res.key_names[k].c_str());
+    }
+  }
+  return KP_OK;
+}
+
+static int32_t SolveRun(kp_solve_plan* plan, kp_cancel* cancel, bool explain, kp_solve_result** out) {
   auto t0 = std::chrono::steady_clock::now();
   if (!plan || !out) return fail(KP_E_INVAL, "null argument");
+  if (explain && plan->a.res_mode)
+    return fail(KP_E_UNSUPPORTED, "explained Solves over capacity reservations are not implemented");
   if (cancel && cancel->ctx.p != plan->ctx.p) return fail(KP_E_INVAL, "the cancel token belongs to another context");
   kp_ctx* ctx = plan->ctx;
   std::lock_guard<std::recursive_mutex> lock(ctx->mu);
@@ -4063,6 +4196,10 @@ int32_t kp_solve_run_cancellable(kp_solve_plan* plan, kp_cancel* cancel, kp_solv
   HIPCHK(hipEventRecord(ctx->ev2, st));
   HIPCHK(launch_finalize(f, st));
   HIPCHK(hipEventRecord(ctx->ev3, st));
+  if (explain) {
+    HIPCHK(hipMemsetAsync(base + plan->o_mark, 0, plan->n_mark, st));
+    HIPCHK(launch_explain(plan->ex, st));
+  }
 
   auto res = std::make_unique<kp_solve_result>();
   ArenaResult ar;
@@ -4076,6 +4213,8 @@ int32_t kp_solve_run_cancellable(kp_solve_plan* plan, kp_cancel* cancel, kp_solv
   if (int32_t rc = AssembleResult(*C.B, stats, ar, P, opt_stride, [](int p) { return p; },
                                   [&](int pos) { return pos < (int)C.ex_input.size() ? C.ex_input[pos] : -1; }, *res))
     return rc;
+  if (explain)
+    if (int32_t rc = FetchReasons(plan, st, *res)) return rc;
   memset(&res->stats, 0, sizeof res->stats);
   res->stats.device_ms = ms_solve + ms_fin;
   res->stats.solve_kernel_ms = ms_solve;
@@ -4119,6 +4258,45 @@ int32_t kp_solve_cancellable(kp_ctx* ctx, const kp_solve_in* in, kp_cancel* canc
   rc = kp_solve_run_cancellable(plan, cancel, out);
   kp_solve_plan_destroy(plan);
   return rc;
+}
+int32_t kp_solve_explained(kp_ctx* ctx, const kp_solve_in* in, kp_cancel* cancel, kp_solve_result** out) {
+  kp_solve_plan* plan = nullptr;
+  int32_t rc = kp_solve_prepare(ctx, in, &plan);
+  if (rc) return rc;
+  rc = kp_solve_run_explained(plan, cancel, out);
+  kp_solve_plan_destroy(plan);
+  return rc;
+}
+int32_t kp_result_explained(const kp_solve_result* r) { return r && r->explained ? 1 : 0; }
+uint32_t kp_result_reason_count(const kp_solve_result* r, uint32_t pod) {
+  if (!r || !r->explained || pod >= r->pod_row.size() || r->pod_row[pod] < 0) return 0;
+  return (uint32_t)r->n_tmpl;
+}
+int32_t kp_result_pod_reasons(const kp_solve_result* r, uint32_t pod, kp_pool_reason* out, uint32_t n) {
+  if (!r || (!out && n)) return fail(KP_E_INVAL, "null argument");
+  if (!r->explained) return fail(KP_E_INVAL, "the result was not explained (kp_solve_run_explained)");
+  if (pod >= r->pod_row.size()) return fail(KP_E_INVAL, "pod %u of %zu", pod, r->pod_row.size());
+  const int row = r->pod_row[pod];
+  const uint32_t cnt = row < 0 ? 0 : std::min<uint32_t>(n, (uint32_t)r->n_tmpl);
+  for (uint32_t t = 0; t < cnt; t++) {
+    const size_t i = (size_t)row * r->n_tmpl + t;
+    const ExplainRec& x = r->why[i];
+    kp_pool_reason& o = out[t];
+    memset(&o, 0, sizeof o);
+    o.nodepool = r->why_nodepool[t];
+    o.code = x.code;
+    o.taint = x.code == KP_WHY_TAINT ? r->why_taint[i] : -1;
+    o.n_types = (uint32_t)x.n_types;
+    o.n_requirements = (uint32_t)x.n_req, o.n_fits = (uint32_t)x.n_fits, o.n_offering = (uint32_t)x.n_off;
+    o.n_requirements_fits = (uint32_t)x.n_rf, o.n_requirements_offering = (uint32_t)x.n_ro;
+    o.n_fits_offering = (uint32_t)x.n_fo, o.n_remaining = (uint32_t)x.n_remaining;
+    auto it = r->why_keys.find(i);
+    if (it != r->why_keys.end()) {
+      o.n_keys = (uint32_t)it->second.size();
+      o.keys = it->second.data();
+    }
+  }
+  return KP_OK;
 }
 
 uint32_t kp_result_nodeclaim_count(const kp_solve_result* r) { return r ? (uint32_t)r->ncs.size() : 0; }

@@ -6221,3 +6221,297 @@ hipError_t launch_feasibility(const FeasArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 #endif  // KP_TU & 2
+#if KP_TU & 1
+// ------------------------------------------------------------------------------------------------
+// The explanation step behind a Solve (kp_solve_run_explained): what addToNewNodeClaim reports, per NodePool template,
+// for every pod the Solve left unscheduled, at the state solve_kernel ended in (remaining limits, topology counts, the
+// pods' final relaxation levels). Pods of one shape-level share their explanation, so the records are per
+// (shape-level, template). Neither kernel writes anything the Solve reads: the plan runs again to the same result.
+// ------------------------------------------------------------------------------------------------
+// explain_mark_kernel: the final shape-level of every unscheduled pod, marked in a byte table (every writer stores 1).
+__global__ __launch_bounds__(256) void explain_mark_kernel(ExplainArgs a) {
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < a.n_pods; p += gridDim.x * 256) {
+    int row = -1;
+    if (a.placement[p] == -1) {
+      row = a.shape_level_base[a.pod_shape[p]] + a.pod_level[p];
+      if (row < 0 || row >= a.n_sl) row = -1;  // (never: levels stay below shape_nlevels)
+      else a.mark[row] = 1;
+    }
+    a.pod_row[p] = row;
+  }
+}
+
+// The keys Requirements.Compatible(A, B, allow_wk) fails on: merge_compatible's two tests without its early return.
+__device__ uint64_t compatible_fail_keys(const DevDict& D, const KReqs* Ak, const KReqs* B, uint64_t b_negop, bool allow_wk,
+                                         WaveSlots* slots, const VInt& vint) {
+  const int lane = LANE;
+  const CandReq A = load_cand(D, Ak);
+  const int k = lane < D.W ? (int)D.wkey[lane] : -1;
+  const uint64_t aP = A.P, bP = B->present;
+  const uint64_t shared = aP & bP;
+  uint64_t undef = bP & ~aP & ~b_negop;
+  if (allow_wk) undef &= ~D.wellknown;
+  const uint64_t a_v = A.v;
+  const uint64_t b_v = lane < D.W ? B->vals[lane] : 0;
+  const uint64_t aC = A.C & aP, bC = B->compl_ & bP;
+  bool hg = false, hl = false, dneb = false;
+  if (lane < D.KB) {
+    const bool inA = (aP >> lane) & 1, inB = (bP >> lane) & 1;
+    const bool agt = inA && ((A.hgt >> lane) & 1), bgt = inB && ((B->hgt >> lane) & 1);
+    const bool alt = inA && ((A.hlt >> lane) & 1), blt = inB && ((B->hlt >> lane) & 1);
+    hg = agt || bgt;
+    hl = alt || blt;
+    const int64_t g = agt && bgt ? max(A.gt, B->gt[lane]) : (agt ? A.gt : (bgt ? B->gt[lane] : 0));
+    const int64_t l = alt && blt ? min(A.lt, B->lt[lane]) : (alt ? A.lt : (blt ? B->lt[lane] : 0));
+    dneb = inA && inB && hg && hl && g >= l;
+    slots->gt[lane] = g;
+    slots->lt[lane] = l;
+  }
+  const uint64_t hgt_any = __ballot(hg), hlt_any = __ballot(hl), dne = __ballot(dneb);
+  wave_sync();
+  uint64_t v = 0;
+  if (k >= 0 && ((shared >> k) & 1)) {
+    const bool c1 = (aC >> k) & 1, c2 = (bC >> k) & 1;
+    v = (c1 && c2) ? (a_v | b_v) : c1 ? (b_v & ~a_v) : c2 ? (a_v & ~b_v) : (a_v & b_v);
+    if ((dne >> k) & 1) v = 0;
+  }
+  const uint64_t bk = (hgt_any | hlt_any) & shared & ~dne;
+  if (bk) v &= bounds_mask(D, bk, hgt_any, hlt_any, slots->gt, slots->lt, vint);
+  const uint64_t compl_new = ((aC & bC) | (aC & ~bP) | (bC & ~aP)) & ~dne;
+  const uint64_t nz = nz_keys(D, v);
+  const uint64_t empty = shared & (dne | (~compl_new & ~nz));
+  const uint64_t negA = negop_mask(aP, aC, nz_keys(D, a_v));
+  wave_sync();
+  return undef | (empty & ~(negA & b_negop));
+}
+
+// solve_kernel's per-pod staging of a shape-level's owned topology groups, on one wave: acc = the domains each
+// dictionary-key group accepts at the current counts (spread: count + self - min <= maxSkew; anti-affinity: empty
+// domains; affinity: domains holding a selected pod, or the self-selecting bootstrap), the counts to LDS.
+__device__ void explain_stage_groups(const ExplainArgs& a, int own_n, int own_base, TopoOwn* town, uint64_t* tacc,
+                                     int32_t (*tcnt)[64]) {
+  const int lane = LANE;
+  for (int j = 0; j < own_n; j++) {
+    const int oi = own_base + j;
+    const int4 r0 = a.own_rec[2 * oi], r1 = a.own_rec[2 * oi + 1];
+    const int g = r0.x, self = r0.y, k = r0.z, mskew = r0.w;
+    uint64_t acc = 0;
+    bool boot = false;
+    if (k >= 0) {
+      const int c = a.tg_cnt[(size_t)g * 64 + lane];
+      const uint64_t reg = a.tg_reg[g], pd = a.own_pd[oi];
+      const bool sup = ((reg & pd) >> lane) & 1;
+      const int mn = wave_min_i32(sup ? c : INT32_MAX);
+      const int num = __builtin_popcountll(reg & pd);
+      int64_t m = num ? (int64_t)mn : (int64_t)INT32_MAX;
+      const int mind = r1.x;
+      if (mind > 0 && num < mind) m = 0;
+      if (mskew > 0) {
+        acc = __ballot(((reg >> lane) & 1) && (int64_t)c + self - m <= mskew);
+      } else if (mskew == 0) {
+        acc = __ballot(((reg >> lane) & 1) && c == 0);
+      } else {
+        acc = __ballot(sup && c > 0);
+        boot = !acc && self;
+        if (boot) acc = reg & pd;
+      }
+      tcnt[j][lane] = c;
+    }
+    const int self_eff = mskew >= 0 ? self : k < 0 ? (self && !(a.tg_reg[g] & 1)) : (boot ? 1 : 0);
+    if (lane == 0) {
+      town[j] = TopoOwn{g, self_eff, k, r1.y, mskew, r1.z};
+      tacc[j] = acc;
+    }
+  }
+  wave_sync();
+}
+
+// Step 1 of filter_types alone, as row pushes: Intersects(type, merged) for the keys the pod (or topology) changed.
+__device__ __forceinline__ void explain_req_rows(const DevDict& D, const CatHdr LDS* H, RowBatch& L, uint64_t& X,
+                                                 uint64_t pod_keys, uint64_t generic_keys, uint64_t negM, uint64_t allowed,
+                                                 const uint64_t* pvp, const int32_t* pvp_slot) {
+  const int TW = D.TW;
+  uint64_t keys = pod_keys & D.catalog_keys;
+  while (keys) {
+    const int k = __builtin_ctzll(keys);
+    keys &= keys - 1;
+    const bool ng = (negM >> k) & 1;
+    if (((D.single_valued & ~generic_keys) >> k) & 1) {
+      rl_push(L, X, TW, pvp + (size_t)pvp_slot[k] * TW, !ng);
+      if (ng) rl_push(L, X, TW, H->d.DNE + (size_t)k * TW, true);
+    } else {
+      rl_push(L, X, TW, H->d.NOKEY + (size_t)k * TW, false);
+      if (ng) rl_push(L, X, TW, H->d.DNE + (size_t)k * TW, false);
+      const int nw = (D.nval[k] + 63) >> 6;
+      for (int wi = 0; wi < nw; wi++) {
+        const int w = key_word(D, k, wi);
+        uint64_t av = lane_bcast(allowed, w);
+        while (av) {
+          const int b = __builtin_ctzll(av);
+          av &= av - 1;
+          rl_push(L, X, TW, H->d.TM + (size_t)(w * 64 + b) * TW, false);
+        }
+      }
+      L.endm |= 1u << (L.n - 1);
+    }
+  }
+}
+
+// explain_kernel: one wave per marked (shape-level, template) pair, grid-strided. In addToNewNodeClaim's order: the
+// limits filter, the taints, Compatible (and the keys it fails on), the topology narrowing of a fresh NodeClaim, then
+// filterInstanceTypesByRequirements' three criteria each on its own over the limit-filtered options, and minValues on
+// the options passing all three. The first cause that holds is the record's code (enum kp_why).
+#define EX_WAVES 4
+__global__ __launch_bounds__(EX_WAVES * 64) void explain_kernel(ExplainArgs a) {
+  __shared__ DevDict D;
+  __shared__ WaveSlots slots[EX_WAVES];
+  __shared__ uint32_t s_scratch[EX_WAVES][2 * KP_MAX_WORDS];
+  __shared__ RowPtr s_rl[EX_WAVES][RL_CAP];
+  __shared__ CatHdr s_hdr[EX_WAVES];
+  __shared__ int64_t s_vint[KP_MAX_BOUND_KEYS * 64];
+  __shared__ TopoOwn s_town[EX_WAVES][8];
+  __shared__ uint64_t s_tacc[EX_WAVES][8];
+  __shared__ int32_t s_tcnt[EX_WAVES][8][64];
+  block_copy(D, a.dict);
+  __syncthreads();
+  for (int i = threadIdx.x; i < D.KB * 64; i += EX_WAVES * 64) s_vint[i] = a.vint[i];
+  __syncthreads();
+  const VInt vi{(const int64_t LDS*)s_vint, a.vint, D.KB};
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = LANE;
+  const int NTm = a.n_tmpl, TW = D.TW, T = D.T;
+  // bits of types >= T in the last word never count
+  const int left = T - lane * 64;
+  const uint64_t valid = lane >= TW || left <= 0 ? 0 : left >= 64 ? ~0ull : (1ull << left) - 1;
+  const long last = (long)a.n_sl * NTm;
+  for (long pr = (long)blockIdx.x * EX_WAVES + wave; pr < last; pr += (long)gridDim.x * EX_WAVES) {
+    const int sl = (int)(pr / NTm), t = (int)(pr % NTm);
+    if (!a.mark[sl]) continue;
+    const int shape = a.sl_shape[sl];
+    const int cat = a.tmpl_catalog[t];
+    wave_sync();
+    hdr_fill_wave((CatHdr LDS*)&s_hdr[wave], &a.cats[cat], D.C);
+    wave_sync();
+    const CatHdr LDS* H = (const CatHdr LDS*)&s_hdr[wave];
+    // filterByRemainingResources at the remaining limits the Solve ended with (never the tmpl_xlim cache)
+    uint64_t X = (lane < TW ? a.tmpl_X[(size_t)t * TW + lane] : 0) & valid;
+    const uint32_t lim = a.tmpl_limit_present[t];
+    if (lim) {
+      const int64_t* rem = a.tmpl_remaining + (size_t)t * KP_NRES;
+      uint64_t keep = 0;
+      for (int i = 0; i < TW; i++) {
+        const uint64_t w = lane_bcast(X, i);
+        if (!w) continue;
+        const int ty = i * 64 + lane;
+        bool viable = ((w >> lane) & 1) && ty < T;
+        for (uint32_t rm = lim; rm && viable; rm &= rm - 1) {
+          const int r = __builtin_ctz(rm);
+          viable = H->d.cap[(size_t)r * T + ty] <= rem[r];
+        }
+        const uint64_t bal = __ballot(viable);
+        if (lane == i) keep = bal;
+      }
+      X = keep;
+    }
+    ExplainRec rec;
+    rec.code = KP_WHY_NONE;
+    rec.n_types = wave_sum(__builtin_popcountll(X));
+    rec.n_req = rec.n_fits = rec.n_off = rec.n_rf = rec.n_ro = rec.n_fo = rec.n_remaining = rec.pad_ = 0;
+    rec.keys = 0;
+    const KReqs* B = kreq_at(a.shape_reqs, sl);
+    const KReqs* A = kreq_at(a.tmpl_reqs, t);
+    const uint64_t b_negop = a.shape_negop[sl];
+    uint64_t m_v = 0;
+    ReqView rv;
+    if (lim && rec.n_types == 0) {
+      rec.code = KP_WHY_LIMITS;
+    } else if (!((a.shape_tolerates[sl] >> a.tmpl_taintset[t]) & 1)) {
+      rec.code = KP_WHY_TAINT;
+    } else if (!merge_compatible(D, A, B, b_negop, true, m_v, rv, &slots[wave], vi)) {
+      rec.code = KP_WHY_REQUIREMENTS;
+      wave_sync();
+      rec.keys = compatible_fail_keys(D, A, B, b_negop, true, &slots[wave], vi);
+    } else {
+      const int own_n = min(a.sl_own_n[sl], 8);
+      const uint64_t topo_keys = own_n ? a.sl_topo_keys[sl] : 0;
+      bool ok = true;
+      if (own_n) {
+        explain_stage_groups(a, own_n, a.sl_own_base[sl], s_town[wave], s_tacc[wave], s_tcnt[wave]);
+        ok = topo_narrow(D, own_n, s_town[wave], s_tacc[wave], s_tcnt[wave], true, m_v, rv, vi);
+        for (int j = 0; j < own_n && ok; j++)  // a fresh node has no count: pod affinity only by bootstrap
+          if (s_town[wave][j].key < 0 && s_town[wave][j].maxskew < 0 && !s_town[wave][j].self) ok = false;
+      }
+      if (!ok) {
+        rec.code = KP_WHY_TOPOLOGY;
+      } else {
+        // the three criteria, each from the limit-filtered set. The template's options already pass every key the pod
+        // did not touch and, when the pod names no offering key, the offerings: an untouched criterion's mask is X
+        const uint64_t pod_keys = B->present | topo_keys;
+        const uint64_t negM = negop_mask(rv.present, rv.compl_, rv.nz);
+        const uint64_t allowed = allowed_word(D, rv, m_v, vi);
+        const uint64_t* pvp = a.shape_pvp + (size_t)a.pvp_base[sl * a.n_catalogs + cat] * TW;
+        uint64_t R = X, F = X, O = X, nb = 0;
+        {
+          RowBatch L{(RowPtr LDS*)s_rl[wave], 0, 0, 0};
+          explain_req_rows(D, H, L, R, pod_keys, topo_keys, negM, allowed, pvp, a.pvp_slot + (size_t)sl * KP_MAX_KEYS);
+          rl_flush(L, R, TW);
+        }
+        {
+          RowBatch L{(RowPtr LDS*)s_rl[wave], 0, 0, 0};
+          const int64_t q_lane = lane < KP_NRES ? a.tmpl_daemon[(size_t)t * KP_NRES + lane] +
+                                                      a.shape_requests[(size_t)shape * KP_NRES + lane]
+                                                : 0;
+          bool zero = false;
+          fits_rows(D, H, L, F, q_lane, 0, nullptr, a.req_res_mask, nb, zero);
+          rl_flush(L, F, TW);
+          if (zero) F = 0;
+        }
+        if (pod_keys & D.offer_keys) {
+          RowBatch L{(RowPtr LDS*)s_rl[wave], 0, 0, 0};
+          const uint64_t cls = D.C <= HDR_CLS ? allowed_classes(D, H->cls, rv, allowed, negM)
+                                              : allowed_classes(D, H->d.cls, rv, allowed, negM);
+          uint64_t m = cls;
+          while (m) {
+            const int c = __builtin_ctzll(m);
+            m &= m - 1;
+            rl_push(L, O, TW, H->d.offer_avail + (size_t)c * TW, m == 0);
+          }
+          rl_flush(L, O, TW);
+          if (!cls) O = 0;
+        }
+        R &= valid, F &= valid, O &= valid;
+        const uint64_t all = R & F & O;
+        rec.n_req = wave_sum(__builtin_popcountll(R));
+        rec.n_fits = wave_sum(__builtin_popcountll(F));
+        rec.n_off = wave_sum(__builtin_popcountll(O));
+        rec.n_rf = wave_sum(__builtin_popcountll(R & F));
+        rec.n_ro = wave_sum(__builtin_popcountll(R & O));
+        rec.n_fo = wave_sum(__builtin_popcountll(F & O));
+        rec.n_remaining = wave_sum(__builtin_popcountll(all));
+        if (rec.n_remaining == 0) {
+          rec.code = KP_WHY_INSTANCE_TYPES;
+        } else if ((rv.hmin & rv.present) &&
+                   !minvalues_ok(D, H->d.code, H->d.TM, rv.hmin & rv.present, rv.minv, all, s_scratch[wave])) {
+          rec.code = KP_WHY_MIN_VALUES;
+        } else {  // the attempt would succeed at the final state
+          rec.n_req = rec.n_fits = rec.n_off = rec.n_rf = rec.n_ro = rec.n_fo = rec.n_remaining = 0;
+        }
+      }
+    }
+    if (rec.code == KP_WHY_LIMITS) rec.n_types = 0;
+    if (lane == 0) a.rec[pr] = rec;
+  }
+}
+
+hipError_t launch_explain(const ExplainArgs& a, hipStream_t s) {
+  if (a.n_pods <= 0 || a.n_sl <= 0) return hipSuccess;
+  const int mblocks = (int)std::min<long>(((long)a.n_pods + 255) / 256, 1024);
+  hipLaunchKernelGGL(explain_mark_kernel, dim3(mblocks), dim3(256), 0, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const long pairs = (long)a.n_sl * a.n_tmpl;
+  if (pairs <= 0) return hipSuccess;
+  const int blocks = (int)std::min<long>((pairs + EX_WAVES - 1) / EX_WAVES, 4096);
+  hipLaunchKernelGGL(explain_kernel, dim3(blocks), dim3(EX_WAVES * 64), 0, s, a);
+  return hipGetLastError();
+}
+#endif  // KP_TU & 1

@@ -90,6 +90,11 @@ def load_lib(path=None):
         "kp_result_nodeclaim": (C.c_int32, [C.c_void_p, C.c_uint32, P(abi.NodeClaimInfo)]),
         "kp_result_stats": (C.c_int32, [C.c_void_p, P(abi.SolveStats)]),
         "kp_result_destroy": (None, [C.c_void_p]),
+        "kp_solve_explained": (C.c_int32, [C.c_void_p, P(abi.SolveIn), C.c_void_p, P(C.c_void_p)]),
+        "kp_solve_run_explained": (C.c_int32, [C.c_void_p, C.c_void_p, P(C.c_void_p)]),
+        "kp_result_explained": (C.c_int32, [C.c_void_p]),
+        "kp_result_reason_count": (C.c_uint32, [C.c_void_p, C.c_uint32]),
+        "kp_result_pod_reasons": (C.c_int32, [C.c_void_p, C.c_uint32, P(abi.PoolReason), C.c_uint32]),
         "kp_simulate_batch": (C.c_int32, [C.c_void_p, P(abi.Cluster), P(C.c_uint32), P(C.c_uint32), C.c_uint32,
                                           C.c_int32, P(abi.SimResult), P(abi.SolveStats)]),
         "kp_cluster_prepare": (C.c_int32, [C.c_void_p, P(abi.Cluster), P(C.c_void_p)]),
@@ -274,6 +279,24 @@ def read_result(lib, res, n_pods, prefix="kp_result_"):
     return {"placement": placement, "nodeclaims": ncs, "stats": stats_dict(st)}
 
 
+def read_reasons(lib, res, placement):
+    """result["reasons"] of an explained kp_solve_result: for every unscheduled pod (placement -1), one dict per
+    NodePool template in the Solve's template order: nodepool, code (abi.KP_WHY_*), taint, keys and the counts."""
+    out = {}
+    for p in np.flatnonzero(placement == -1):
+        n = lib.kp_result_reason_count(res, int(p))
+        buf = (abi.PoolReason * max(1, n))()
+        _check_generic(lib, lib.kp_result_pod_reasons(res, int(p), buf, n))
+        rows = []
+        for r in buf[:n]:
+            d = {"nodepool": int(r.nodepool), "code": int(r.code), "taint": int(r.taint),
+                 "keys": [r.keys[i].decode() for i in range(r.n_keys)]}
+            d.update({f: int(getattr(r, f)) for f in abi.REASON_COUNTS})
+            rows.append(d)
+        out[int(p)] = rows
+    return out
+
+
 def stats_dict(st):
     d = {f: getattr(st, f) for f, _ in abi.SolveStats._fields_}
     d["phase_cycles"] = list(st.phase_cycles)
@@ -305,16 +328,24 @@ class Scheduler:
             self._si = abi.build_solve_in(self._arena, self.problem, catalog_handles=[c.h.value for c in self.catalogs])
         return self._si
 
-    def solve(self, read=True):
+    def solve(self, read=True, explain=False):
         """kp_solve: compile the per-Solve half (the catalogue half comes resident from the ctx cache after the first
-        Solve on these catalogues + NodePools), upload, run, copy the results back. read=False returns stats only."""
+        Solve on these catalogues + NodePools), upload, run, copy the results back. read=False returns stats only.
+        explain=True: kp_solve_explained; the result's "reasons" maps every unscheduled pod to its per-NodePool
+        reasons (read_reasons)."""
         lib = self.ctx.lib
         si = self.solve_in()
         res = C.c_void_p()
-        _check(lib, lib.kp_solve(self.ctx.h, C.byref(si), C.byref(res)))
+        if explain:
+            _check(lib, lib.kp_solve_explained(self.ctx.h, C.byref(si), None, C.byref(res)))
+        else:
+            _check(lib, lib.kp_solve(self.ctx.h, C.byref(si), C.byref(res)))
         try:
             if read:
-                return read_result(lib, res, self.problem.n_pods)
+                out = read_result(lib, res, self.problem.n_pods)
+                if explain:
+                    out["reasons"] = read_reasons(lib, res, out["placement"])
+                return out
             st = abi.SolveStats()
             lib.kp_result_stats(res, C.byref(st))
             return {"stats": stats_dict(st)}
@@ -368,17 +399,24 @@ class SolvePlan:
             _check(lib, lib.kp_solve_prepare_comm(sched.ctx.h, C.byref(si), comm.h, C.byref(h)))
         self.h = h
 
-    def run(self, read=True, cancel=None):
-        """kp_solve_run; with a Cancel token, kp_solve_run_cancellable (KPError KP_E_CANCELED once it is set)."""
+    def run(self, read=True, cancel=None, explain=False):
+        """kp_solve_run; with a Cancel token, kp_solve_run_cancellable (KPError KP_E_CANCELED once it is set).
+        explain=True: kp_solve_run_explained (the token optional); the result's "reasons" maps every unscheduled pod
+        to its per-NodePool reasons (read_reasons)."""
         lib = self.sched.ctx.lib
         res = C.c_void_p()
-        if cancel is None:
+        if explain:
+            _check(lib, lib.kp_solve_run_explained(self.h, cancel.h if cancel is not None else None, C.byref(res)))
+        elif cancel is None:
             _check(lib, lib.kp_solve_run(self.h, C.byref(res)))
         else:
             _check(lib, lib.kp_solve_run_cancellable(self.h, cancel.h, C.byref(res)))
         try:
             if read:
-                return read_result(lib, res, self.sched.problem.n_pods)
+                out = read_result(lib, res, self.sched.problem.n_pods)
+                if explain:
+                    out["reasons"] = read_reasons(lib, res, out["placement"])
+                return out
             st = abi.SolveStats()
             lib.kp_result_stats(res, C.byref(st))
             return {"stats": stats_dict(st)}

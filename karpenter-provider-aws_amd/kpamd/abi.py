@@ -184,6 +184,23 @@ class NodeClaimInfo(C.Structure):
                 ("requests", ResourceList), ("requirements", Requirements)]
 
 
+KP_WHY_NONE, KP_WHY_LIMITS, KP_WHY_TAINT, KP_WHY_REQUIREMENTS, KP_WHY_TOPOLOGY, KP_WHY_INSTANCE_TYPES, \
+    KP_WHY_MIN_VALUES = range(7)
+
+
+class PoolReason(C.Structure):
+    """kp_pool_reason: why one NodePool template cannot take an unscheduled pod (explained Solves)."""
+    _fields_ = [("nodepool", C.c_uint32), ("code", C.c_int32), ("taint", C.c_int32), ("n_types", C.c_uint32),
+                ("n_requirements", C.c_uint32), ("n_fits", C.c_uint32), ("n_offering", C.c_uint32),
+                ("n_requirements_fits", C.c_uint32), ("n_requirements_offering", C.c_uint32),
+                ("n_fits_offering", C.c_uint32), ("n_remaining", C.c_uint32), ("n_keys", C.c_uint32),
+                ("keys", C.POINTER(C.c_char_p))]
+
+
+REASON_COUNTS = ("n_types", "n_requirements", "n_fits", "n_offering", "n_requirements_fits", "n_requirements_offering",
+                 "n_fits_offering", "n_remaining")
+
+
 class SolveStats(C.Structure):
     _fields_ = [("device_ms", C.c_double), ("host_ms", C.c_double), ("prepare_ms", C.c_double),
                 ("solve_kernel_ms", C.c_double), ("finalize_kernel_ms", C.c_double), ("attempts", C.c_uint64),
