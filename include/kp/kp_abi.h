@@ -28,6 +28,8 @@
  *                             price filters, requirements, requests, pods) and where every rescheduled pod went.
  *   kp_cluster_validate    <- upstream Validation.ValidateCommand: the command re-simulated on a plan of current state
  *                             and accepted only if the new simulation agrees with it.
+ *   kp_cluster_candidates  <- upstream disruption GetCandidates: which nodes a method may disrupt, why not the others
+ *                             (do-not-disrupt, PDBs, consolidateAfter, ...), and the disruption-cost order.
  *
  * Conventions
  *   - Every function returns int32: KP_OK (0) or a negative KP_E_* code. kp_last_error() gives text.
@@ -1101,6 +1103,132 @@ typedef struct kp_validation {
 int32_t kp_cluster_validate(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
                             uint32_t n_subsets, const kp_command_check* checks, const uint32_t* allowed,
                             uint32_t n_allowed, kp_validation* out, uint64_t* n_blocked, kp_solve_stats* stats);
+/* Disruption candidates (upstream disruption.GetCandidates: NewCandidate per node, pdb.Limits, utils/disruption
+ * ReschedulingCost / LifetimeRemaining / DisruptionCost, then the methods' sort), additive to ABI v13. Those upstream
+ * files are not among this project's references: the rule is RESTATED here from
+ * R:website/content/en/preview/concepts/disruption.md (:84-86 policy and consolidateAfter, :99-103 the ordering
+ * preferences, :105-113 the Unconsolidatable events, :259-267 terminationGracePeriod, :335-396 PDBs and do-not-disrupt)
+ * and parity beyond it is unpinned: the upstream pod-list order behind `detail`, the name tie-break, and whatever
+ * NewCandidate checks beyond this text. Every input is per snapshot; the plan is one kp_cluster_prepare made of it.
+ *
+ * Eviction cost of a pod, exact in fixed point (units of 2^-27):
+ *   fx = clamp(2^27 + deletion_cost + 4 * priority, -10 * 2^27, +10 * 2^27)
+ * which is upstream's 1.0 + deletionCost / 2^27 + priority / 2^25 clamped to [-10, 10]; an absent annotation or a nil
+ * priority is 0. ReschedulingCost(node) = the int64 sum of fx over the node's reschedulable pods (kp_cluster_node.pods):
+ * every term is a multiple of 2^-27 and the sum stays far below 2^53, so its value as a double is exact and does not
+ * depend on the order of summation. The device sums integers.
+ *   LifetimeRemaining = 1.0 when expire_after_s < 0 (Never), 0.0 when expire_after_s == 0, else
+ *                       clamp(double(expire_after_s - (now - created)) / double(expire_after_s), 0, 1)
+ *   DisruptionCost    = (double(sum fx) * 2^-27) * LifetimeRemaining, in IEEE double (both are reported for every node)
+ * Times are unix seconds; differences of two of them must fit int64.
+ *
+ * Reason of a node: the first line that applies; KP_CANDIDATE (0) makes it a candidate. detail is the reason's argument
+ * (0 where it has none).
+ *    1 KP_NOT_MANAGED             no karpenter.sh/nodepool label, or it names no NodePool of the cluster
+ *    2 KP_NODE_DO_NOT_DISRUPT     KP_NODE_DO_NOT_DISRUPT set (the node's karpenter.sh/do-not-disrupt annotation)
+ *    3 KP_NOT_INITIALIZED         kp_existing_node.initialized == 0
+ *    4 KP_DELETING                kp_cluster_node.deleting
+ *    5 KP_NOMINATED               KP_NODE_NOMINATED set (nominated for a pending pod)
+ *    6 KP_POD_DO_NOT_DISRUPT      some pod of the node has KP_POD_DO_NOT_DISRUPT; detail = the cluster pod index of the
+ *                                 first such pod in the node's `pods` order
+ *    7 KP_PDB_BLOCKED             some pod has a PDB of its namespace whose selector matches its labels and whose
+ *                                 disruptions_allowed == 0; detail = the PDB index: the lowest blocking PDB of the first
+ *                                 blocked pod in `pods` order. Every pod is checked for 6 before any for 7.
+ *    8 KP_CONSOLIDATION_DISABLED  Emptiness / SingleNode / MultiNode, and the pool's consolidate_after_s < 0 (Never)
+ *    9 KP_POLICY_WHEN_EMPTY       SingleNode / MultiNode, and the pool's policy is KP_WHEN_EMPTY
+ *   10 KP_NOT_CONSOLIDATABLE      Emptiness / SingleNode / MultiNode, and now - last_pod_event < consolidate_after_s
+ *   11 KP_NOT_EMPTY               Emptiness, and the node has a reschedulable pod
+ *   12 KP_NOT_DRIFTED             Drift, and KP_NODE_DRIFTED is not set
+ * 6 and 7 are skipped for Drift on a node with KP_NODE_TERMINATION_GRACE_PERIOD (disruption.md:259). A nil selector
+ * matches nothing, an empty one every pod of the PDB's namespace; a pod matching several PDBs is blocked if any blocks.
+ *
+ * Order: the candidates ascend by DisruptionCost compared as Go compares float64 (-0.0 and +0.0 tie; the cost is never
+ * NaN), for Drift by drifted_unix instead; ties go by node name bytes, then node index (the project's convention).
+ * order[0 .. *n_candidates) holds their node indices; out[i] is node i's record whatever its reason.
+ *
+ * Errors: KP_E_INVAL for a count that differs from the plan's snapshot (n_pools, n_nodes, n_pods), a NULL array whose
+ * count is not 0, a NULL out / order / n_candidates, an unknown method or selector operator, a NULL selector key, and a
+ * node of the snapshot listing a pod or a pod naming a shape out of range; the stale-plan refusal of
+ * kp_cluster_simulate (kp_catalog_update_offerings until kp_cluster_refresh, a destroyed catalogue). KP_E_UNSUPPORTED
+ * (the Go path then runs) for 65,535 or more NodePools (the node -> pool table is 16 bits wide), 2^28 or more distinct
+ * labels and label keys over the shapes, and 2^31 or more selector terms; no cap on PDBs, nodes or pods beyond those of
+ * kp_cluster_prepare. The call reads the snapshot's names, labels, namespaces and pod lists only: it works on plans of
+ * both simulation paths, compiles them on its first use and keeps them resident, and leaves kp_cluster_simulate* and
+ * every other call on the plan untouched. stats: device_ms (the kernels), host_ms (the call). */
+enum kp_disruption_method {
+  KP_METHOD_EMPTINESS = 0,
+  KP_METHOD_SINGLE_NODE = 1,
+  KP_METHOD_MULTI_NODE = 2,
+  KP_METHOD_DRIFT = 3
+};
+enum kp_consolidation_policy { KP_WHEN_EMPTY_OR_UNDERUTILIZED = 0, KP_WHEN_EMPTY = 1 };
+enum kp_candidate_reason {
+  KP_CANDIDATE = 0,
+  KP_NOT_MANAGED = 1,
+  KP_NODE_DO_NOT_DISRUPT_REASON = 2,
+  KP_NOT_INITIALIZED = 3,
+  KP_DELETING = 4,
+  KP_NOMINATED = 5,
+  KP_POD_DO_NOT_DISRUPT_REASON = 6,
+  KP_PDB_BLOCKED = 7,
+  KP_CONSOLIDATION_DISABLED = 8,
+  KP_POLICY_WHEN_EMPTY = 9,
+  KP_NOT_CONSOLIDATABLE = 10,
+  KP_NOT_EMPTY = 11,
+  KP_NOT_DRIFTED = 12
+};
+typedef struct kp_pool_disruption {   /* NodePool spec.disruption, indexed like kp_cluster.nodepools */
+  int32_t policy;                     /* enum kp_consolidation_policy */
+  int32_t reserved_;
+  int64_t consolidate_after_s;        /* < 0: Never */
+} kp_pool_disruption;
+#define KP_NODE_DO_NOT_DISRUPT 1u
+#define KP_NODE_NOMINATED 2u
+#define KP_NODE_TERMINATION_GRACE_PERIOD 4u
+#define KP_NODE_DRIFTED 8u
+typedef struct kp_node_disruption {   /* indexed like kp_cluster.nodes */
+  uint32_t flags;                     /* KP_NODE_* */
+  uint32_t reserved_;
+  int64_t created_unix;               /* the NodeClaim's creationTimestamp */
+  int64_t expire_after_s;             /* < 0: Never */
+  int64_t last_pod_event_unix;        /* status.lastPodEventTime */
+  int64_t drifted_unix;               /* transition time of the Drifted condition (read when KP_NODE_DRIFTED) */
+} kp_node_disruption;
+#define KP_POD_DO_NOT_DISRUPT 1u
+typedef struct kp_pod_disruption {    /* indexed like kp_cluster.pods */
+  int32_t priority;                   /* spec.priority; nil: 0 */
+  int32_t deletion_cost;              /* controller.kubernetes.io/pod-deletion-cost; absent: 0 */
+  uint32_t flags;                     /* KP_POD_* */
+  uint32_t reserved_;
+} kp_pod_disruption;
+typedef struct kp_pdb {
+  const char* namespace_;
+  const char* name;                   /* for the caller's events; not read */
+  kp_label_selector selector;
+  int32_t disruptions_allowed;        /* status.disruptionsAllowed: 0 blocks every pod the PDB selects */
+  int32_t reserved_;
+} kp_pdb;
+typedef struct kp_candidates_in {
+  const kp_pool_disruption* pools;
+  const kp_node_disruption* nodes;
+  const kp_pod_disruption* pods;
+  const kp_pdb* pdbs;
+  uint32_t n_pools;                   /* == kp_cluster.n_nodepools */
+  uint32_t n_nodes;                   /* == kp_cluster.n_nodes */
+  uint32_t n_pods;                    /* == kp_cluster.n_pods */
+  uint32_t n_pdbs;
+  int64_t now_unix;
+  int32_t method;                     /* enum kp_disruption_method */
+  int32_t reserved_;
+} kp_candidates_in;
+typedef struct kp_candidate {
+  int32_t reason;                     /* enum kp_candidate_reason */
+  uint32_t detail;
+  int64_t rescheduling_cost_fx;       /* sum of fx, units of 2^-27 */
+  double disruption_cost;
+} kp_candidate;
+int32_t kp_cluster_candidates(kp_cluster_plan* plan, const kp_candidates_in* in, kp_candidate* out /* n_nodes */,
+                              uint32_t* order /* n_nodes */, uint32_t* n_candidates, kp_solve_stats* stats);
 /* The reduction kp_consolidate_argmin applies to the gathered per-rank records (host-only; exposed for callers that
  * reduce over another transport, and for tests): counts are summed, the best record wins. */
 int32_t kp_choice_reduce(const kp_choice* per_rank, uint32_t n, kp_choice* out);

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "kp/kp_abi.h"
+#include "kp_cand.h"
 #include "kp_device.h"
 #include "kp_model.h"
 
@@ -5056,6 +5057,18 @@ struct OwnedCluster {
   }
 };
 
+// kp_cluster_candidates: what the call compiles from the snapshot on its first use and keeps resident (the nodes' pod
+// CSR, the pods' shapes, the nodes' name ranks and static reason bits, the shapes' label bitsets and namespace ids), the
+// dictionaries a call's PDB selectors are compiled against, and the buffer its per-call arrays and results live in.
+struct CandState {
+  DevBuf buf;
+  CandArgs a{};                                   // the resident half of the kernel arguments
+  std::unordered_map<string, uint32_t> atom_id;   // "P" key NUL value: a label pair of some shape; "K" key: a label key
+  std::unordered_map<string, uint32_t> ns_id;     // the shapes' namespaces
+  DevBuf call;
+  size_t call_bytes = 0;
+};
+
 struct GeneralBatch;
 struct kp_cluster_plan {
   CtxRef ctx;
@@ -5097,6 +5110,7 @@ struct kp_cluster_plan {
   vector<uint16_t> node_pool;
   const uint16_t* d_node_pool = nullptr;  // its resident copy (batched path)
   uint32_t n_pools = 0;
+  std::unique_ptr<CandState> cand;        // kp_cluster_candidates, built on its first call
 };
 
 // kp_*_budgeted: the caller's allowed[] and the count of subsets it blocked
@@ -7927,6 +7941,239 @@ int32_t kp_cluster_validate(kp_cluster_plan* plan, kp_cancel* cancel, const uint
       stats->phase_cycles[1] = plan->sim_waves[0];
       stats->phase_cycles[2] = plan->sim_waves[1];
     }
+  }
+  return KP_OK;
+}
+
+// ---- Disruption candidates (kp_cluster_candidates) ----------------------------------------------------------------
+// The host does strings only: name ranks, the label dictionary and the shapes' bitsets once per plan, the PDB selectors
+// compiled against that dictionary per call. Reasons, costs and the order are the device's (kp_cand.hip).
+static_assert(sizeof(CandPool) == sizeof(kp_pool_disruption) && sizeof(CandNode) == sizeof(kp_node_disruption) &&
+                  sizeof(CandPod) == sizeof(kp_pod_disruption) && sizeof(CandOut) == sizeof(kp_candidate),
+              "the device records mirror the ABI's");
+static_assert(sizeof(kp_candidate) == 24 && sizeof(kp_node_disruption) == 40 && sizeof(kp_pod_disruption) == 16, "ABI sizes");
+
+static string PairAtom(const char* key, const char* value) {
+  string k = "P";
+  k += key;
+  k += '\0';
+  k += value ? value : "";
+  return k;
+}
+
+static int32_t CandBuild(kp_cluster_plan* plan) {
+  kp_ctx* ctx = plan->ctx;
+  const kp_cluster& cl = plan->cluster()->cl;
+  const uint32_t N = cl.n_nodes, P = cl.n_pods, S = cl.n_shapes;
+  if (plan->n_pools >= 0xFFFF)
+    return fail(KP_E_UNSUPPORTED, "candidates over %u NodePools (max 65534)", plan->n_pools);
+  auto cs = std::make_unique<CandState>();
+  vector<uint32_t> off(N + 1, 0), pods, pod_shape(P), st(N), rank(N), inv(N);
+  for (uint32_t i = 0; i < N; i++) {
+    const kp_cluster_node& n = cl.nodes[i];
+    if (n.n_pods && !n.pods) return fail(KP_E_INVAL, "node %u: null pods", i);
+    for (uint32_t j = 0; j < n.n_pods; j++) {
+      if (n.pods[j] >= P) return fail(KP_E_INVAL, "node %u lists pod %u of %u", i, n.pods[j], P);
+      pods.push_back(n.pods[j]);
+    }
+    if (pods.size() > 0xFFFFFFFFull) return fail(KP_E_UNSUPPORTED, "more than 2^32 pod references");
+    off[i + 1] = (uint32_t)pods.size();
+    const uint16_t pool = plan->node_pool[i];
+    st[i] = (pool == 0xFFFF ? CAND_ST_UNMANAGED : 0) | (n.node.initialized ? 0 : CAND_ST_UNINITIALIZED) |
+            (n.deleting ? CAND_ST_DELETING : 0) | ((uint32_t)pool << 16);
+  }
+  for (uint32_t p = 0; p < P; p++) {
+    if (cl.pods[p].shape >= S) return fail(KP_E_INVAL, "pod %u names shape %u of %u", p, cl.pods[p].shape, S);
+    pod_shape[p] = cl.pods[p].shape;
+  }
+  {  // name ranks: bytes, then index, so that they are distinct
+    auto name = [&](uint32_t i) { return std::string_view(cl.nodes[i].node.name ? cl.nodes[i].node.name : ""); };
+    for (uint32_t i = 0; i < N; i++) inv[i] = i;
+    std::sort(inv.begin(), inv.end(), [&](uint32_t x, uint32_t y) {
+      const int c = name(x).compare(name(y));
+      return c != 0 ? c < 0 : x < y;
+    });
+    for (uint32_t r = 0; r < N; r++) rank[inv[r]] = r;
+  }
+  vector<uint32_t> shape_ns(S);
+  vector<vector<uint32_t>> shape_atoms(S);
+  for (uint32_t s = 0; s < S; s++) {
+    const kp_pod_shape& sh = cl.shapes[s];
+    if (sh.n_labels && !sh.labels) return fail(KP_E_INVAL, "shape %u: null labels", s);
+    shape_ns[s] = cs->ns_id.emplace(sh.namespace_ ? sh.namespace_ : "", (uint32_t)cs->ns_id.size()).first->second;
+    for (uint32_t j = 0; j < sh.n_labels; j++) {
+      if (!sh.labels[j].key) return fail(KP_E_INVAL, "shape %u: null label key", s);
+      auto& ids = cs->atom_id;
+      shape_atoms[s].push_back(ids.emplace(PairAtom(sh.labels[j].key, sh.labels[j].value), (uint32_t)ids.size()).first->second);
+      shape_atoms[s].push_back(ids.emplace(string("K") + sh.labels[j].key, (uint32_t)ids.size()).first->second);
+    }
+  }
+  if (cs->atom_id.size() >= (1u << 28))
+    return fail(KP_E_UNSUPPORTED, "%zu distinct labels and label keys over the shapes (max 2^28 - 1)", cs->atom_id.size());
+  const int W = (int)std::max<size_t>(1, (cs->atom_id.size() + 63) / 64);
+  vector<uint64_t> bits((size_t)S * W, 0);
+  for (uint32_t s = 0; s < S; s++)
+    for (uint32_t id : shape_atoms[s]) bits[(size_t)s * W + (id >> 6)] |= 1ull << (id & 63);
+  Blob blob;
+  const size_t o_off = blob.put(off), o_pods = blob.put(pods), o_shape = blob.put(pod_shape), o_st = blob.put(st),
+               o_rank = blob.put(rank), o_inv = blob.put(inv), o_bits = blob.put(bits), o_ns = blob.put(shape_ns);
+  HIPCHK(cs->buf.alloc(blob.total()));
+  uint8_t* base = (uint8_t*)cs->buf.p;
+  HIPCHK(hipMemcpyAsync(base, blob.host.data(), blob.host.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  CandArgs& a = cs->a;
+  a.node_off = (const uint32_t*)(base + o_off), a.node_pods = (const uint32_t*)(base + o_pods);
+  a.pod_shape = (const uint32_t*)(base + o_shape), a.node_static = (const uint32_t*)(base + o_st);
+  a.node_rank = (const uint32_t*)(base + o_rank), a.rank_node = (const uint32_t*)(base + o_inv);
+  a.shape_bits = (const uint64_t*)(base + o_bits), a.shape_ns = (const uint32_t*)(base + o_ns);
+  a.n_shapes = (int)S, a.words = W, a.n_nodes = (int)N;
+  uint64_t pad = CAND_TILE;
+  while (pad < N) pad <<= 1;
+  a.n_pad = (uint32_t)pad;
+  plan->cand = std::move(cs);
+  return KP_OK;
+}
+
+// One PDB's selector as tokens over the plan's dictionary; *can_match = false when it can select no pod of the snapshot
+static int32_t CandCompileSelector(const CandState& cs, const kp_label_selector& sel, uint32_t p, vector<uint32_t>& tok,
+                                   bool* can_match) {
+  *can_match = false;
+  if (sel.is_nil) return KP_OK;
+  if ((sel.n_match_labels && !sel.match_labels) || (sel.n_match_expressions && !sel.match_expressions))
+    return fail(KP_E_INVAL, "pdb %u: null selector array", p);
+  auto atom = [&](const string& k) {
+    auto f = cs.atom_id.find(k);
+    return f == cs.atom_id.end() ? CAND_NONE : f->second;
+  };
+  const size_t start = tok.size();
+  bool ok = true;
+  for (uint32_t j = 0; j < sel.n_match_labels; j++) {
+    if (!sel.match_labels[j].key) return fail(KP_E_INVAL, "pdb %u: null selector key", p);
+    const uint32_t id = atom(PairAtom(sel.match_labels[j].key, sel.match_labels[j].value));
+    if (id == CAND_NONE) ok = false;
+    else tok.push_back(CAND_TOK_MUST | id);
+  }
+  for (uint32_t j = 0; j < sel.n_match_expressions; j++) {
+    const kp_selector_requirement& e = sel.match_expressions[j];
+    if (!e.key) return fail(KP_E_INVAL, "pdb %u: null selector key", p);
+    if (e.n_values && !e.values) return fail(KP_E_INVAL, "pdb %u: null selector values", p);
+    for (uint32_t v = 0; v < e.n_values; v++)
+      if (!e.values[v]) return fail(KP_E_INVAL, "pdb %u: null selector value", p);
+    switch (e.op) {
+      case KP_SEL_IN: {
+        const size_t first = tok.size();
+        for (uint32_t v = 0; v < e.n_values; v++) {
+          const uint32_t id = atom(PairAtom(e.key, e.values[v]));
+          if (id != CAND_NONE) tok.push_back(CAND_TOK_ANY | id);
+        }
+        if (tok.size() == first) ok = false;
+        else tok.back() |= CAND_TOK_END;
+        break;
+      }
+      case KP_SEL_NOT_IN:
+        for (uint32_t v = 0; v < e.n_values; v++) {
+          const uint32_t id = atom(PairAtom(e.key, e.values[v]));
+          if (id != CAND_NONE) tok.push_back(CAND_TOK_MUSTNOT | id);
+        }
+        break;
+      case KP_SEL_EXISTS:
+      case KP_SEL_DOES_NOT_EXIST: {
+        const uint32_t id = atom(string("K") + e.key);
+        if (id != CAND_NONE) tok.push_back((e.op == KP_SEL_EXISTS ? CAND_TOK_MUST : CAND_TOK_MUSTNOT) | id);
+        else if (e.op == KP_SEL_EXISTS) ok = false;
+        break;
+      }
+      default:
+        return fail(KP_E_INVAL, "pdb %u: selector operator %d", p, e.op);
+    }
+  }
+  if (!ok) tok.resize(start);
+  *can_match = ok;
+  return KP_OK;
+}
+
+int32_t kp_cluster_candidates(kp_cluster_plan* plan, const kp_candidates_in* in, kp_candidate* out, uint32_t* order,
+                              uint32_t* n_candidates, kp_solve_stats* stats) {
+  if (n_candidates) *n_candidates = 0;
+  if (!plan || !in || !n_candidates) return fail(KP_E_INVAL, "null argument");
+  kp_ctx* ctx = plan->ctx;
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  HIPCHK(hipSetDevice(ctx->device));
+  if (stats) memset(stats, 0, sizeof *stats);
+  const auto t0 = std::chrono::steady_clock::now();
+  const OwnedCluster* oc = plan->cluster();
+  if (!oc) return fail(KP_E_INVAL, "the plan holds no cluster");
+  if (plan->general) {
+    if (int32_t rc = CatalogsAlive(oc->alive)) return rc;
+  } else {  // a plan of the batched simulation kernel: kp_cluster_simulate's stale-plan refusal
+    if (int32_t rc = CatalogsAlive(plan->cp->B->alive)) return rc;
+    if (SeqnumsOf(plan->cp->B->catalogs) != plan->cp->B->seqnums)
+      return fail(KP_E_INVAL, "stale plan: a catalogue's seqnum changed since it was prepared (kp_cluster_refresh)");
+  }
+  const kp_cluster& cl = oc->cl;
+  if (in->n_pools != cl.n_nodepools || in->n_nodes != cl.n_nodes || in->n_pods != cl.n_pods)
+    return fail(KP_E_INVAL, "candidates for %u NodePools, %u nodes, %u pods; the plan's snapshot has %u, %u, %u", in->n_pools,
+                in->n_nodes, in->n_pods, cl.n_nodepools, cl.n_nodes, cl.n_pods);
+  if ((in->n_pools && !in->pools) || (in->n_nodes && !in->nodes) || (in->n_pods && !in->pods) || (in->n_pdbs && !in->pdbs))
+    return fail(KP_E_INVAL, "null pools, nodes, pods or pdbs");
+  if (in->n_nodes && (!out || !order)) return fail(KP_E_INVAL, "null out or order");
+  if (in->method < KP_METHOD_EMPTINESS || in->method > KP_METHOD_DRIFT) return fail(KP_E_INVAL, "method %d", in->method);
+  if (!plan->cand)
+    if (int32_t rc = CandBuild(plan)) return rc;
+  CandState& cs = *plan->cand;
+  const uint32_t N = in->n_nodes, B = in->n_pdbs;
+  // the PDBs against the plan's dictionary
+  vector<uint32_t> pdb_ns(B), tok_off(B + 1, 0), tok;
+  vector<uint8_t> blocks(B, 0);
+  for (uint32_t p = 0; p < B; p++) {
+    const kp_pdb& b = in->pdbs[p];
+    bool can = false;
+    if (int32_t rc = CandCompileSelector(cs, b.selector, p, tok, &can)) return rc;
+    if (tok.size() >= (1ull << 31)) return fail(KP_E_UNSUPPORTED, "2^31 or more selector terms");
+    tok_off[p + 1] = (uint32_t)tok.size();
+    auto f = cs.ns_id.find(b.namespace_ ? b.namespace_ : "");
+    pdb_ns[p] = f == cs.ns_id.end() ? CAND_NONE : f->second;
+    blocks[p] = can && b.disruptions_allowed == 0 && pdb_ns[p] != CAND_NONE;
+  }
+  if (N == 0) return KP_OK;
+  CandArgs a = cs.a;
+  Blob blob;
+  const size_t o_pools = blob.put(in->pools, in->n_pools), o_nodes = blob.put(in->nodes, N),
+               o_pods = blob.put(in->pods, in->n_pods), o_pns = blob.put(pdb_ns), o_blk = blob.put(blocks),
+               o_toff = blob.put(tok_off), o_tok = blob.put(tok);
+  const size_t o_verdict = blob.reserve_dev(sizeof(uint32_t) * std::max(a.n_shapes, 1)),
+               o_out = blob.reserve_dev(sizeof(CandOut) * N), o_keys = blob.reserve_dev(sizeof(uint64_t) * a.n_pad),
+               o_ranks = blob.reserve_dev(sizeof(uint32_t) * a.n_pad), o_order = blob.reserve_dev(sizeof(uint32_t) * N),
+               o_n = blob.reserve_dev(sizeof(uint32_t));
+  if (blob.total() > cs.call_bytes) {
+    HIPCHK(cs.call.alloc(blob.total()));
+    cs.call_bytes = blob.total();
+  }
+  uint8_t* base = (uint8_t*)cs.call.p;
+  a.pools = (const CandPool*)(base + o_pools), a.nodes = (const CandNode*)(base + o_nodes);
+  a.pods = (const CandPod*)(base + o_pods), a.pdb_ns = (const uint32_t*)(base + o_pns);
+  a.pdb_blocks = base + o_blk, a.pdb_tok_off = (const uint32_t*)(base + o_toff), a.pdb_tok = (const uint32_t*)(base + o_tok);
+  a.n_pdbs = (int)B;
+  a.verdict = (uint32_t*)(base + o_verdict), a.out = (CandOut*)(base + o_out), a.keys = (uint64_t*)(base + o_keys);
+  a.ranks = (uint32_t*)(base + o_ranks), a.order = (uint32_t*)(base + o_order), a.n_cand = (uint32_t*)(base + o_n);
+  a.now = in->now_unix, a.method = in->method;
+  hipStream_t st = ctx->stream;
+  HIPCHK(hipMemcpyAsync(base, blob.host.data(), blob.host.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(hipEventRecord(ctx->ev0, st));
+  HIPCHK(launch_candidates(a, st));
+  HIPCHK(hipEventRecord(ctx->ev1, st));
+  uint32_t n = 0;
+  HIPCHK(hipMemcpyAsync(out, a.out, sizeof(CandOut) * N, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(order, a.order, sizeof(uint32_t) * N, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&n, a.n_cand, sizeof n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (n > N) return fail(KP_E_DEVICE, "the device counted %u candidates of %u nodes", n, N);
+  *n_candidates = n;
+  if (stats) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    stats->device_ms = ms;
+    stats->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
   return KP_OK;
 }

@@ -7,6 +7,7 @@ The surfaces mirror the reference's plugin/operator interface for the path:
   ClusterPlan(...).simulate(subsets)          <- upstream disruption computeConsolidation / SimulateScheduling
   ClusterPlan(...).drift(subsets)             <- upstream disruption Drift: SimulateScheduling, the whole Solve
   ClusterPlan(...).command(subsets)           <- computeConsolidation's Command: the replacement NodeClaim + placements
+  ClusterPlan(...).candidates(method, now)    <- upstream disruption GetCandidates: reasons, costs and the order
 Everything computes behind the C ABI on the GPU; a missing libkp.so or HIP device raises.
 """
 import ctypes as C
@@ -133,6 +134,8 @@ def load_lib(path=None):
         "kp_cluster_validate": (C.c_int32, [C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32), C.c_uint32,
                                             P(abi.CommandCheck), P(C.c_uint32), C.c_uint32, P(abi.Validation),
                                             P(C.c_uint64), P(abi.SolveStats)]),
+        "kp_cluster_candidates": (C.c_int32, [C.c_void_p, P(abi.CandidatesIn), C.c_void_p, P(C.c_uint32), P(C.c_uint32),
+                                              P(abi.SolveStats)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name, None)
@@ -826,6 +829,24 @@ class ClusterPlan:
         if allowed is not None:
             sd["budget_blocked"] = int(blocked.value)
         return [{f: int(getattr(out[i], f)) for f, _ in abi.Validation._fields_} for i in range(n)], sd
+
+    def candidates(self, method, now, controls=None):
+        """kp_cluster_candidates for one method (abi.METHOD_*) at unix time now, on controls (default: the cluster's
+        DisruptionControls). Returns (records, order, stats): records the numpy array of abi.candidate_dtype(), one per
+        node (reason 0: a candidate); order the candidates' node indices in disruption order."""
+        controls = self.cluster.controls if controls is None else controls
+        if controls is None:
+            raise ValueError("the cluster carries no DisruptionControls")
+        arena = Arena()
+        ci = abi.build_candidates_in(arena, controls, method, now)
+        n = len(self.cluster.nodes)
+        out = np.zeros(max(n, 1), dtype=abi.candidate_dtype())
+        order = np.zeros(max(n, 1), dtype=np.uint32)
+        count, st = C.c_uint32(0), abi.SolveStats()
+        _check(self.ctx.lib, self.ctx.lib.kp_cluster_candidates(self.h, C.byref(ci), out.ctypes.data,
+                                                                order.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                                C.byref(count), C.byref(st)))
+        return out[:n], [int(x) for x in order[:count.value]], stats_dict(st)
 
     def close(self):
         if self.h:

@@ -307,6 +307,75 @@ class Validation(C.Structure):
                 ("n_unscheduled", C.c_uint32), ("n_missing", C.c_uint32), ("blocked", C.c_uint32)]
 
 
+class PoolDisruption(C.Structure):
+    _fields_ = [("policy", C.c_int32), ("reserved_", C.c_int32), ("consolidate_after_s", C.c_int64)]
+
+
+class Pdb(C.Structure):
+    _fields_ = [("namespace_", C.c_char_p), ("name", C.c_char_p), ("selector", LabelSelector),
+                ("disruptions_allowed", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class CandidatesIn(C.Structure):
+    _fields_ = [("pools", C.POINTER(PoolDisruption)), ("nodes", C.c_void_p), ("pods", C.c_void_p),
+                ("pdbs", C.POINTER(Pdb)), ("n_pools", C.c_uint32), ("n_nodes", C.c_uint32), ("n_pods", C.c_uint32),
+                ("n_pdbs", C.c_uint32), ("now_unix", C.c_int64), ("method", C.c_int32), ("reserved_", C.c_int32)]
+
+
+# enum kp_disruption_method, kp_consolidation_policy, kp_candidate_reason; KP_NODE_* / KP_POD_* flags
+METHOD_EMPTINESS, METHOD_SINGLE_NODE, METHOD_MULTI_NODE, METHOD_DRIFT = range(4)
+POLICIES = {"WhenEmptyOrUnderutilized": 0, "WhenEmpty": 1}
+REASON_NAMES = ("CANDIDATE", "NOT_MANAGED", "NODE_DO_NOT_DISRUPT", "NOT_INITIALIZED", "DELETING", "NOMINATED",
+                "POD_DO_NOT_DISRUPT", "PDB_BLOCKED", "CONSOLIDATION_DISABLED", "POLICY_WHEN_EMPTY", "NOT_CONSOLIDATABLE",
+                "NOT_EMPTY", "NOT_DRIFTED")
+NODE_DO_NOT_DISRUPT, NODE_NOMINATED, NODE_TERMINATION_GRACE_PERIOD, NODE_DRIFTED = 1, 2, 4, 8
+POD_DO_NOT_DISRUPT = 1
+
+
+def node_disruption_dtype():
+    import numpy as np
+    return np.dtype([("flags", "<u4"), ("r", "<u4"), ("created_unix", "<i8"), ("expire_after_s", "<i8"),
+                     ("last_pod_event_unix", "<i8"), ("drifted_unix", "<i8")])
+
+
+def pod_disruption_dtype():
+    import numpy as np
+    return np.dtype([("priority", "<i4"), ("deletion_cost", "<i4"), ("flags", "<u4"), ("r", "<u4")])
+
+
+def candidate_dtype():
+    """kp_candidate"""
+    import numpy as np
+    return np.dtype([("reason", "<i4"), ("detail", "<u4"), ("rescheduling_cost_fx", "<i8"), ("disruption_cost", "<f8")])
+
+
+def build_candidates_in(arena, controls, method, now):
+    """kpamd.model.DisruptionControls -> kp_candidates_in (buffers kept by the arena)."""
+    import numpy as np
+    pools = arena.arr(PoolDisruption, [PoolDisruption(POLICIES[p.policy], 0,
+                                                      -1 if p.consolidate_after is None else int(p.consolidate_after))
+                                       for p in controls.pools])
+    nodes = np.zeros(len(controls.nodes), dtype=node_disruption_dtype())
+    for i, n in enumerate(controls.nodes):
+        nodes[i] = ((NODE_DO_NOT_DISRUPT if n.do_not_disrupt else 0) | (NODE_NOMINATED if n.nominated else 0) |
+                    (NODE_TERMINATION_GRACE_PERIOD if n.termination_grace_period else 0) |
+                    (NODE_DRIFTED if n.drifted is not None else 0), 0, int(n.created),
+                    -1 if n.expire_after is None else int(n.expire_after), int(n.last_pod_event),
+                    0 if n.drifted is None else int(n.drifted))
+    pods = np.zeros(len(controls.pod_priority), dtype=pod_disruption_dtype())
+    pods["priority"] = controls.pod_priority
+    pods["deletion_cost"] = controls.pod_deletion_cost
+    pods["flags"] = np.where(np.asarray(controls.pod_do_not_disrupt, dtype=bool), POD_DO_NOT_DISRUPT, 0)
+    pdbs = arena.arr(Pdb, [Pdb(arena.s(b.namespace), arena.s(b.name), arena.selector(b.selector),
+                               int(b.disruptions_allowed), 0) for b in controls.pdbs])
+    arena.keep.extend([nodes, pods])
+    ci = CandidatesIn(pools, nodes.ctypes.data if len(nodes) else None, pods.ctypes.data if len(pods) else None,
+                      pdbs if controls.pdbs else None, len(controls.pools), len(nodes), len(pods), len(controls.pdbs),
+                      int(now), int(method), 0)
+    arena.keep.append(ci)
+    return ci
+
+
 # enum kp_validity
 (VALID, INVALID_UNSCHEDULED, INVALID_NO_REPLACEMENT_NEEDED, INVALID_MULTIPLE, INVALID_NEEDS_REPLACEMENT,
  INVALID_NOT_SUBSET, INVALID_BUDGET) = range(7)

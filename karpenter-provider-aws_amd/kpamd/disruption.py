@@ -26,6 +26,10 @@ CS3 and R:website/content/en/preview/concepts/disruption.md:89-128):
   Controller.compute_command(cluster, plan) one disruption pass in upstream order ("first Drift then Consolidation",
                                             disruption.md:16-27; Emptiness, Drift, MultiNodeConsolidation,
                                             SingleNodeConsolidation): the first method that returns a command wins
+  candidates(cluster, plan, method, now)    GetCandidates on the device (kp_cluster_candidates) when the cluster carries
+                                            DisruptionControls: per node the reason it is no candidate (do-not-disrupt,
+                                            PDBs, consolidateAfter, ...), the costs, and the candidates in disruption
+                                            order; Controller.compute_command takes its lists from it then
   Validation(cluster, plan)                 Validation.IsValid of a computed command against a FRESH snapshot (upstream
   Controller.validate(cmd, old, new, plan)  disruption/validation.go, restated in DESIGN §12): the candidates mapped by
                                             node name (gone, deleting, nominated, the budget walk), then one
@@ -82,6 +86,21 @@ def candidate_order(cluster, nodes=None):
     sorts a slice built from a map: parity unpinned)."""
     idx = [i for i in (range(len(cluster.nodes)) if nodes is None else nodes) if not cluster.nodes[i].deleting]
     return sorted(idx, key=lambda i: (len(cluster.nodes[i].pods), cluster.nodes[i].node.name))
+
+
+METHODS = {"emptiness": 0, "single": 1, "multi": 2, "drift": 3}  # enum kp_disruption_method
+
+
+def candidates(cluster, plan, method, now):
+    """GetCandidates for one method ("emptiness" / "single" / "multi" / "drift", or its kp_disruption_method value) at
+    unix time `now`, from cluster.controls (DisruptionControls): (records, order). records[i] is node i's
+    kp_candidate (reason 0: a candidate, else why not, with the reason's detail; ReschedulingCost in units of 2^-27;
+    DisruptionCost); order lists the candidates by DisruptionCost (Drift: by the Drifted transition time), ties by node
+    name. plan: the resident snapshot (ClusterPlan, or any object with the same candidates(method, now))."""
+    if cluster.controls is None:
+        raise ValueError("the cluster carries no DisruptionControls (candidate_order / drift_order apply)")
+    res = plan.candidates(METHODS.get(method, method), int(now))
+    return res[0], list(res[1])
 
 
 # ---- NodePool disruption budgets -----------------------------------------------------------------------------------
@@ -296,8 +315,8 @@ class Drift:
     wins, with every new NodeClaim of that Solve as its replacements (none: a plain delete). All candidates are one
     plan.drift batch of singletons: the device answers which is first."""
 
-    def compute_command(self, cluster, plan, now=None, not_ready=(), extra_deleting=None):
-        cands = drift_order(cluster)
+    def compute_command(self, cluster, plan, now=None, not_ready=(), extra_deleting=None, cands=None):
+        cands = drift_order(cluster) if cands is None else list(cands)
         if not cands:
             return None
         allowed = None
@@ -351,6 +370,8 @@ class Controller:
         return Command(method, candidates, r["decision"], out)
 
     def compute_command(self, cluster, plan, now=None, not_ready=(), extra_deleting=None):
+        if getattr(cluster, "controls", None) is not None:
+            return self._compute_with_controls(cluster, plan, now, not_ready, extra_deleting)
         cands = candidate_order(cluster)
         cmd = Emptiness().compute_command(cluster, cands, now, not_ready, extra_deleting)
         if cmd is not None:
@@ -359,6 +380,25 @@ class Controller:
         if cmd is not None:
             return cmd
         cands = [c for c in cands if cluster.nodes[c].pods]
+        return self._consolidate(cluster, plan, cands, cands, now, not_ready, extra_deleting)
+
+    def _compute_with_controls(self, cluster, plan, now, not_ready, extra_deleting):
+        """The pass with each method's candidates from candidates() (cluster.controls set): the same methods in the
+        same order, every list the device's for that method at `now`."""
+        at = int(_ts(now))
+        cmd = Emptiness().compute_command(cluster, candidates(cluster, plan, "emptiness", at)[1], now, not_ready,
+                                          extra_deleting)
+        if cmd is not None:
+            return cmd
+        cmd = Drift().compute_command(cluster, plan, now, not_ready, extra_deleting,
+                                      cands=candidates(cluster, plan, "drift", at)[1])
+        if cmd is not None:
+            return cmd
+        multi = [c for c in candidates(cluster, plan, "multi", at)[1] if cluster.nodes[c].pods]
+        single = [c for c in candidates(cluster, plan, "single", at)[1] if cluster.nodes[c].pods]
+        return self._consolidate(cluster, plan, multi, single, now, not_ready, extra_deleting)
+
+    def _consolidate(self, cluster, plan, cands, single_cands, now, not_ready, extra_deleting):
         allowed = None
         if budgets_modelled(cluster):
             allowed = allowed_disruptions(cluster, UNDERUTILIZED, now, not_ready, extra_deleting)
@@ -367,7 +407,7 @@ class Controller:
         if hit is not None:
             n, r = hit
             return self._materialized(plan, "multi", multi.candidates(cands)[:n], r)
-        hit = SingleNodeConsolidation(plan, cluster, allowed).compute_command(cands)
+        hit = SingleNodeConsolidation(plan, cluster, allowed).compute_command(single_cands)
         if hit is not None:
             c, r = hit
             return self._materialized(plan, "single", [c], r)

@@ -142,6 +142,56 @@ class ClusterNode:
 
 
 @dataclass
+class PodDisruptionBudget:
+    """policyv1.PodDisruptionBudget as disruption reads it: selector None = nil (selects nothing), LabelSelector() =
+    every pod of the namespace; disruptions_allowed is status.disruptionsAllowed (0 blocks the pods it selects)."""
+    namespace: str
+    name: str
+    selector: Optional[LabelSelector] = None
+    disruptions_allowed: int = 0
+
+
+@dataclass
+class PoolControls:
+    """NodePool spec.disruption: consolidationPolicy and consolidateAfter in seconds (None: Never)."""
+    policy: str = "WhenEmptyOrUnderutilized"  # or "WhenEmpty"
+    consolidate_after: Optional[int] = 0
+
+
+@dataclass
+class NodeControls:
+    """What disruption reads of a node and its NodeClaim beyond the snapshot (times in unix seconds)."""
+    do_not_disrupt: bool = False              # the node's karpenter.sh/do-not-disrupt annotation
+    nominated: bool = False                   # nominated for a pending pod
+    termination_grace_period: bool = False    # the NodeClaim has a terminationGracePeriod
+    created: int = 0                          # creationTimestamp
+    expire_after: Optional[int] = None        # expireAfter in seconds (None: Never)
+    last_pod_event: int = 0                   # status.lastPodEventTime
+    drifted: Optional[int] = None             # transition time of the Drifted condition (None: not drifted)
+
+
+@dataclass
+class DisruptionControls:
+    """The inputs of candidate selection (kp_cluster_candidates): pools indexed like Cluster.nodepools, nodes like
+    Cluster.nodes, the pod arrays like Cluster.pod_shape."""
+    pools: List[PoolControls]
+    nodes: List[NodeControls]
+    pod_priority: np.ndarray                  # int32 [P] spec.priority (nil: 0)
+    pod_deletion_cost: np.ndarray             # int32 [P] controller.kubernetes.io/pod-deletion-cost (absent: 0)
+    pod_do_not_disrupt: np.ndarray            # bool [P] the pod's karpenter.sh/do-not-disrupt annotation
+    pdbs: List[PodDisruptionBudget] = field(default_factory=list)
+
+    @classmethod
+    def default(cls, cluster):
+        """Nothing set: every pod at the default priority and deletion cost, no expiry, consolidateAfter 0s; the
+        Drifted times are taken from ClusterNode.drifted."""
+        P = len(cluster.pod_shape)
+        return cls([PoolControls() for _ in cluster.nodepools],
+                   [NodeControls(drifted=None if n.drifted is None else int(n.drifted)) for n in cluster.nodes],
+                   np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, bool))
+
+
+@dataclass
 class Cluster:
     catalogs: List[List[InstanceType]]
     nodepools: List[NodePool]
@@ -156,6 +206,7 @@ class Cluster:
     spot_to_spot: bool = False                         # SpotToSpotConsolidation feature gate
     namespaces: Dict[str, Dict[str, str]] = field(default_factory=dict)  # cluster namespaces: name -> labels
     pod_uid_str: Optional[List[str]] = None  # metadata.uid per pod (kp_cluster.pod_uids): the exact Queue tie-break
+    controls: Optional[DisruptionControls] = None  # None: not modelled (candidate_order / drift_order decide)
 
 
 @dataclass

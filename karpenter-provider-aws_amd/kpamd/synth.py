@@ -765,3 +765,57 @@ def with_disruption_state(cluster, seed, n_deleting=3, n_pending=6, cpu_limit_m=
             np_.limits = {"cpu": int(cpu_limit_m)}
     cl.name = f"{cluster.name}+disruption-state"
     return cl
+
+
+def add_disruption_controls(cluster, seed, n_pdbs=12, now=1_750_100_000):
+    """Randomized DisruptionControls for `cluster` (set as cluster.controls and returned), to be called before the
+    cluster is prepared: shapes without labels get an app and a tier label for the PDB selectors to meet; pools get a
+    policy and a consolidateAfter; nodes do-not-disrupt / nominated / terminationGracePeriod marks, creation, expiry,
+    last pod event and Drifted times around `now` (with ties); pods priorities and deletion costs out to the clamp and a
+    few do-not-disrupt marks; n_pdbs PodDisruptionBudgets over every selector form, some in a namespace without pods."""
+    from .model import DisruptionControls, NodeControls, PodDisruptionBudget, PoolControls
+    rng = np.random.default_rng(seed)
+    for i, sh in enumerate(cluster.shapes):
+        if not sh.labels:
+            sh.labels = {"app": f"app-{i % 8}", "tier": ("web", "db", "batch")[i % 3]}
+    pools = [PoolControls("WhenEmpty" if rng.random() < 0.2 else "WhenEmptyOrUnderutilized",
+                          [0, 0, 30, 3600, None][int(rng.integers(0, 5))]) for _ in cluster.nodepools]
+    nodes = []
+    for _ in cluster.nodes:
+        nodes.append(NodeControls(
+            do_not_disrupt=bool(rng.random() < 0.03), nominated=bool(rng.random() < 0.03),
+            termination_grace_period=bool(rng.random() < 0.3), created=now - int(rng.integers(0, 30 * 86_400)),
+            expire_after=[None, None, 3600, 7 * 86_400, 30 * 86_400, 0][int(rng.integers(0, 6))],
+            last_pod_event=now - int(rng.integers(0, 7200)),
+            drifted=now - 100 * int(rng.integers(0, 50)) if rng.random() < 0.3 else None))
+    P = len(cluster.pod_shape)
+    prio = np.array([0] * 8 + [-100, 1000, 1_000_000, 1_000_000_000, -2**31], dtype=np.int64)
+    cost = np.array([0] * 8 + [100, -100, 2**31 - 1, -(2**31 - 1)], dtype=np.int64)
+    controls = DisruptionControls(pools, nodes, prio[rng.integers(0, len(prio), size=P)].astype(np.int32),
+                                  cost[rng.integers(0, len(cost), size=P)].astype(np.int32), rng.random(P) < 0.004)
+    spaces = sorted({sh.namespace for sh in cluster.shapes}) + ["elsewhere"]
+    pairs = sorted({(k, v) for sh in cluster.shapes for k, v in sh.labels.items()}) or [("app", "none")]
+    for b in range(n_pdbs):
+        k, v = pairs[int(rng.integers(0, len(pairs)))]
+        k2, v2 = pairs[int(rng.integers(0, len(pairs)))]
+        form = int(rng.integers(0, 8))
+        if form == 0:
+            sel = LabelSelector({k: v})
+        elif form == 1:
+            sel = LabelSelector({}, [(k, "In", [v, v2, "absent"])])
+        elif form == 2:
+            sel = LabelSelector({k: v}, [(k2, "NotIn", [v2])])
+        elif form == 3:
+            sel = LabelSelector({k: v}, [(k2, "Exists", [])])
+        elif form == 4:
+            sel = LabelSelector({k: v}, [("missing-key", "DoesNotExist", [])])
+        elif form == 5:
+            sel = None
+        elif form == 6:
+            sel = LabelSelector({k: v, k2: v2})
+        else:
+            sel = LabelSelector() if rng.random() < 0.3 else LabelSelector({k: "absent"})
+        controls.pdbs.append(PodDisruptionBudget(spaces[int(rng.integers(0, len(spaces)))], f"pdb-{b}", sel,
+                                                 [0, 0, 1, 3][int(rng.integers(0, 4))]))
+    cluster.controls = controls
+    return controls
