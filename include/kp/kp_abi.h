@@ -30,6 +30,8 @@
  *                             and accepted only if the new simulation agrees with it.
  *   kp_cluster_candidates  <- upstream disruption GetCandidates: which nodes a method may disrupt, why not the others
  *                             (do-not-disrupt, PDBs, consolidateAfter, ...), and the disruption-cost order.
+ *   kp_cluster_simulate_explained <- the exits of computeConsolidation behind the Unconsolidatable events: the
+ *                             decisions of kp_cluster_simulate_budgeted plus, per subset, which exit made it a no-op.
  *
  * Conventions
  *   - Every function returns int32: KP_OK (0) or a negative KP_E_* code. kp_last_error() gives text.
@@ -1103,6 +1105,84 @@ typedef struct kp_validation {
 int32_t kp_cluster_validate(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets, const uint32_t* nodes,
                             uint32_t n_subsets, const kp_command_check* checks, const uint32_t* allowed,
                             uint32_t n_allowed, kp_validation* out, uint64_t* n_blocked, kp_solve_stats* stats);
+/* Why a subset cannot be consolidated (upstream disruption/consolidation.go, v1.5.1: the exits of
+ * computeConsolidation, each of which publishes an Unconsolidatable event), additive to ABI v13. The upstream file is
+ * not among this project's references: the rule below is RESTATED here from what kp_cluster_simulate already decides,
+ * only the events' two documented texts are pinned (R:website/content/en/preview/concepts/disruption.md:105-113, "pdb
+ * default/inflate-pdb prevents pod evictions" - that one comes from kp_cluster_candidates - and "can't replace with a
+ * lower-priced node"; :119-128 for the spot-to-spot rule and its 15 options), and parity beyond the rule is unpinned.
+ * Inputs, the budget rule, the errors, the stale-plan refusal and cancellation are those of
+ * kp_cluster_simulate_budgeted, and out[s] is bit for bit what that call writes. why[s] is the first line that holds
+ * of subset s's simulation r, in the enum's order:
+ *   NONE                 r decided DELETE or REPLACE
+ *   BUDGET               the budget rule blocked the subset: not simulated, every count 0
+ *   MULTIPLE_NODECLAIMS  r needs a second NodeClaim
+ *   UNSCHEDULABLE        some non-pending pod of r is unscheduled, or a candidate pod sits on an uninitialized node, or
+ *                        the one NodeClaim's truncated options break minValues (Truncate belongs to the Solve: its pods
+ *                        fail) - decided before the candidates' prices and before the spot-to-spot gate are looked at
+ *   UNPRICED             one NodeClaim, and some candidate has no label-compatible offering (getCandidatePrices fails)
+ *   SPOT_TO_SPOT_DISABLED  every candidate is spot, the replacement may launch spot, and the feature gate is off
+ *   NOT_CHEAPER          filterByPrice (worst launch price < the candidates' price) keeps nothing
+ *   SAME_TYPE            multi_node: filterOutSameType keeps nothing
+ *   SPOT_FLEXIBILITY     spot-to-spot with a single candidate and fewer than 15 options left
+ *   MIN_VALUES           a NON-EMPTY filtered set breaks minValues; stage: 1 after filterByPrice, 2 after
+ *                        filterOutSameType (an empty set is NOT_CHEAPER / SAME_TYPE, never MIN_VALUES)
+ * One stated difference from upstream's message order: upstream checks "all pods scheduled" before it counts
+ * NodeClaims. Every consolidation simulation here stops at its second NodeClaim - the pods it had not reached are in no
+ * state yet - so MULTIPLE_NODECLAIMS comes first and carries no unscheduled count (n_nodeclaims 2, n_unscheduled 0,
+ * first_unscheduled -1), the convention kp_cluster_validate documents for its rule 3.
+ * Field rule: a field that belongs to a stage r did not reach is 0 (-1 for the two index fields); every field is
+ * written for every simulation. The stages are the Solve (n_nodeclaims, n_unscheduled, first_unscheduled), Truncate
+ * with minValues held on a fully scheduled r with one NodeClaim (n_truncated, cheapest_launch - whatever the prices and
+ * the gate then say), filterByPrice (n_cheaper; not reached by UNPRICED and SPOT_TO_SPOT_DISABLED) and
+ * filterOutSameType (n_same_type; reached when filterByPrice kept a set that holds minValues; without multi_node it
+ * passes that set on). REPLACE under the spot-to-spot cut reports n_same_type before the cut, out[s].n_options after.
+ * counts (may be NULL): the KP_UNCONS_COUNT-word histogram of why[0 .. n_subsets).reason. why may be NULL when counts
+ * is not: the histogram alone comes back and, on a batched-kernel plan without limits, the records are never read
+ * from the device (a 1M-subset sweep: 80 bytes instead of 48 MB).
+ * On a plan of the batched simulation kernel a fifth sim_kernel instantiation writes out[] and why[] (48 bytes per
+ * simulation) and why_count_kernel the histogram, so a sweep is explained without reading its records back. NodePool
+ * limits on such a plan: the kernel judges a second NodeClaim by the limits the pass began with, while the first
+ * NodeClaim has taken its largest option out of them (subtractMax); the difference between MULTIPLE_NODECLAIMS and
+ * UNSCHEDULABLE is this call's answer, so when some NodePool has limits every record the kernel reports as
+ * MULTIPLE_NODECLAIMS is settled by the subset's own whole Solve: the caller pays one compile and one Solve per such
+ * subset, one after the other on the host (stats->phase_cycles[3] counts them): a sweep over a cluster with limits
+ * whose subsets mostly need a second NodeClaim pays that for most of them, and is better asked for a sample. The record
+ * stays the kernel's where that Solve would change out[s].
+ * On a general-path plan the launches and per-subset Solves of kp_cluster_simulate run, and the decision code fills
+ * the record on the host from each Solve's placements and options. */
+enum kp_unconsolidatable {      /* first that holds, in this order */
+  KP_UNCONS_NONE = 0,                 /* DELETE or REPLACE */
+  KP_UNCONS_BUDGET = 1,               /* blocked by the budget rule: not simulated */
+  KP_UNCONS_MULTIPLE_NODECLAIMS = 2,  /* the simulation needs a second NodeClaim */
+  KP_UNCONS_UNSCHEDULABLE = 3,        /* a non-pending pod is unscheduled, a candidate pod sits on an uninitialized
+                                         node, or the NodeClaim's truncated options break minValues (its pods fail) */
+  KP_UNCONS_UNPRICED = 4,             /* one NodeClaim; some candidate has no label-compatible offering */
+  KP_UNCONS_SPOT_TO_SPOT_DISABLED = 5,
+  KP_UNCONS_NOT_CHEAPER = 6,          /* filterByPrice keeps nothing: "can't replace with a lower-priced node" */
+  KP_UNCONS_SAME_TYPE = 7,            /* multi_node: filterOutSameType keeps nothing */
+  KP_UNCONS_SPOT_FLEXIBILITY = 8,     /* single spot candidate, fewer than 15 options left */
+  KP_UNCONS_MIN_VALUES = 9,           /* a non-empty filtered set breaks minValues; stage says after which filter */
+  KP_UNCONS_COUNT = 10
+};
+typedef struct kp_sim_why {
+  int32_t  reason;             /* enum kp_unconsolidatable */
+  int32_t  stage;              /* MIN_VALUES: 1 after filterByPrice, 2 after filterOutSameType; else 0 */
+  uint32_t n_nodeclaims;       /* 0, 1, or 2 = more than one */
+  uint32_t n_unscheduled;      /* as kp_validation.n_unscheduled; 0 for MULTIPLE and BUDGET */
+  int32_t  first_unscheduled;  /* cluster pod index of the first such pod in queue order (kp_drift_result's rule), -1 */
+  int32_t  unpriced;           /* UNPRICED: position in the subset of the first unpriced candidate; else -1 */
+  uint32_t n_truncated;        /* options of the one NodeClaim after Truncate (minValues held); 0 before that stage */
+  uint32_t n_cheaper;          /* of those, worst launch price < candidate price */
+  uint32_t n_same_type;        /* left after filterOutSameType (= n_cheaper when !multi_node) */
+  uint32_t reserved_;
+  double   cheapest_launch;    /* min worst launch price over the n_truncated options; 0 when n_truncated == 0 */
+} kp_sim_why;
+int32_t kp_cluster_simulate_explained(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets,
+                                      const uint32_t* nodes, uint32_t n_subsets, int32_t multi_node,
+                                      const uint32_t* allowed, uint32_t n_allowed, kp_sim_result* out, kp_sim_why* why,
+                                      uint64_t* counts /* KP_UNCONS_COUNT words, may be NULL */, uint64_t* n_blocked,
+                                      kp_solve_stats* stats);
 /* Disruption candidates (upstream disruption.GetCandidates: NewCandidate per node, pdb.Limits, utils/disruption
  * ReschedulingCost / LifetimeRemaining / DisruptionCost, then the methods' sort), additive to ABI v13. Those upstream
  * files are not among this project's references: the rule is RESTATED here from

@@ -493,12 +493,14 @@ struct SimAll {
   static constexpr bool gated = false;
   static constexpr bool emit = false;
   static constexpr bool check = false;
+  static constexpr bool why = false;
   static constexpr const uint32_t* live = nullptr;
 };
 struct SimLive {
   static constexpr bool gated = true;
   static constexpr bool emit = false;
   static constexpr bool check = false;
+  static constexpr bool why = false;
   const uint32_t* live;
 };
 // The emitting instantiation (kp_cluster_command): gated as SimLive, and every simulation also leaves the command it
@@ -523,6 +525,7 @@ struct SimEmit {
   static constexpr bool gated = true;
   static constexpr bool emit = true;
   static constexpr bool check = false;
+  static constexpr bool why = false;
   const uint32_t* live;
   uint8_t* rec;
   size_t stride;  // sim_cmd_stride(cap)
@@ -541,12 +544,47 @@ struct SimCheck {
   static constexpr bool gated = true;
   static constexpr bool emit = false;
   static constexpr bool check = true;
+  static constexpr bool why = false;
   const uint32_t* live;
   const uint64_t* want;     // [n_subsets][n_catalogs][TW]
   const uint32_t* unknown;  // [n_subsets][n_catalogs]
   const uint8_t* replace;   // [n_subsets] 1: the command carries a replacement
   uint32_t* val;            // [n_subsets] ValOut
 };
+// The explaining instantiation (kp_cluster_simulate_explained): gated as SimLive (the identity list without budgets),
+// decides as SimLive decides and also leaves, at the caller's subset index, which exit of computeConsolidation the
+// simulation took: one WhyOut (kp_sim_why), twelve words, lane w writes word w, plain vector stores. Like SimCheck it
+// counts a candidate pod on an uninitialized node and goes on, and truncates whatever the candidates' prices and the
+// spot-to-spot gate say (Truncate's minValues check is the Solve's, so it is judged before either); unlike SimCheck it
+// then runs the price stages.
+struct WhyOut {
+  int32_t reason, stage;
+  uint32_t n_nodeclaims, n_unscheduled;
+  int32_t first_unscheduled, unpriced;
+  uint32_t n_truncated, n_cheaper, n_same_type, reserved_;
+  double cheapest_launch;
+};
+#define WHY_WORDS 12
+static_assert(sizeof(WhyOut) == 4 * WHY_WORDS, "WhyOut is twelve words");
+struct SimWhy {
+  static constexpr bool gated = true;
+  static constexpr bool emit = false;
+  static constexpr bool check = false;
+  static constexpr bool why = true;
+  const uint32_t* live;
+  uint32_t* rec;  // [n_subsets] WhyOut
+};
+// why_count_kernel: the histogram of the records' reasons in two stages (blocks count contiguous ranges, one block
+// sums the partials; integers, no atomics). A subset the budget gate blocked (gate[s] == 0; gate null: none) was not
+// simulated: the first stage writes its KP_UNCONS_BUDGET record.
+#define WHY_REASONS 10
+#define WHY_COUNT_THREADS 256
+#define WHY_COUNT_MAX_BLOCKS 64
+hipError_t launch_why_count(uint32_t* rec, const uint8_t* gate, int n, uint64_t* part, uint64_t* counts, hipStream_t s);
+inline int why_count_blocks(int n) {
+  const int b = (n + WHY_COUNT_THREADS - 1) / WHY_COUNT_THREADS;
+  return b < 1 ? 1 : (b > WHY_COUNT_MAX_BLOCKS ? WHY_COUNT_MAX_BLOCKS : b);
+}
 inline size_t sim_cmd_stride(int cap) { return (sizeof(SimCmdHdr) + (size_t)12 * cap + 15) & ~(size_t)15; }
 // budget gate over the resident CSR batch (budget_gate_kernel, gate_scan_kernel, gate_scatter_kernel)
 #define GATE_WAVES 4
@@ -652,6 +690,9 @@ const void* sim_emit_kernel_ptr();
 // the checking instantiation (kp_cluster_validate): as launch_sim_gated, with the checks and the verdict records
 hipError_t launch_sim_check(const SimArgs& a, const SimCheck& ck, int n_live, int blocks, size_t dyn_lds, hipStream_t s);
 const void* sim_check_kernel_ptr();
+// the explaining instantiation (kp_cluster_simulate_explained): as launch_sim_gated, with the reason records
+hipError_t launch_sim_why(const SimArgs& a, const SimWhy& wy, int n_live, int blocks, size_t dyn_lds, hipStream_t s);
+const void* sim_why_kernel_ptr();
 #define SIM_WAVES 4
 
 hipError_t launch_solve(const SolveArgs& a, int nw, size_t dyn_lds, hipStream_t s);

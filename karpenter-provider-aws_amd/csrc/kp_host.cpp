@@ -5750,55 +5750,105 @@ struct CandCache {
 // non-pending pod was scheduled (and no candidate pod onto an uninitialized node). The Solve made n_nc NodeClaims;
 // R / ci / nodepool / opts: the first one's final requirements (held reservation ids applied), catalogue, NodePool and
 // price-ordered options (after Truncate), minValues not yet checked on them.
+// why (kp_cluster_simulate_explained, or null): the record of the exit taken, in kp_abi.h's order. The caller has
+// filled the Solve's fields (WhySolve); Truncate's minValues check is judged before the candidates' prices and the
+// spot-to-spot gate, which changes no decision (every one of those exits is a no-op).
+struct WhySolve {
+  kp_sim_why* why = nullptr;
+  uint32_t nc_np = 0;          // non-pending pods on NodeClaim 0 (they fail when its truncated options break minValues)
+  int64_t bad_pos = INT64_MAX; // queue position of first_unscheduled as filled
+  int64_t nc_pos = INT64_MAX;  // queue position and cluster pod of the first non-pending pod on NodeClaim 0
+  int32_t nc_pod = -1;
+};
+static void WhyClear(kp_sim_why* w) {
+  memset(w, 0, sizeof *w);
+  w->first_unscheduled = w->unpriced = -1;
+}
 static void GeneralDecide(const kp_cluster& cl, const vector<std::map<string, string>>& labels,
                           const vector<uint32_t>& cand, const SolveBase& B, bool all, int n_nc, const KReqs* R,
                           int ci, uint32_t nodepool, const uint32_t* opts, uint32_t n_opts, int32_t multi_node,
                           SimOut& r, const OfferTab* tab = nullptr, const CandCache* cc = nullptr,
-                          vector<int>* kept_out = nullptr, bool* s2s_out = nullptr) {
+                          vector<int>* kept_out = nullptr, bool* s2s_out = nullptr, const WhySolve* ws = nullptr) {
+  kp_sim_why* why = ws ? ws->why : nullptr;
   double candPrice = 0;
   bool priced = true, allSpot = true;
-  for (uint32_t c : cand) {
+  int32_t unpriced = -1;
+  for (size_t k = 0; k < cand.size(); k++) {
+    const uint32_t c = cand[k];
     if (cc) {
       priced = priced && cc->priced[c];
+      if (unpriced < 0 && !cc->priced[c]) unpriced = (int32_t)k;
       candPrice += cc->price[c];
       allSpot = allSpot && cc->spot[c];
       continue;
     }
     const kp_cluster_node& n = cl.nodes[c];
     double p = 0;
-    if (!NodeCandidatePrice(cl.catalogs[n.catalog]->types[n.instance_type], labels[c], &p)) priced = false;
+    if (!NodeCandidatePrice(cl.catalogs[n.catalog]->types[n.instance_type], labels[c], &p)) {
+      priced = false;
+      if (unpriced < 0) unpriced = (int32_t)k;
+    }
     candPrice += p;
     auto f = labels[c].find(kCapType);
     if (f == labels[c].end() || f->second != "spot") allSpot = false;
   }
   r.candidate_price = priced ? candPrice : 0;
-  if (!all) return;  // no-op
+  auto exit_as = [&](int32_t reason, int32_t stage = 0) {
+    if (why) why->reason = reason, why->stage = stage;
+  };
+  if (why && n_nc > 1) {  // stopped at (or made) a second NodeClaim: nothing of the unfinished Solve is reported
+    WhyClear(why);
+    why->n_nodeclaims = 2;
+    return exit_as(KP_UNCONS_MULTIPLE_NODECLAIMS);
+  }
+  // (with `why`, a Solve that left pods unscheduled still takes Truncate's minValues check on its one NodeClaim first:
+  // that NodeClaim's pods fail too and are counted, as sim_kernel and a subset's own whole Solve count them)
+  if (!all && (!why || n_nc != 1)) return exit_as(KP_UNCONS_UNSCHEDULABLE);  // no-op
   if (n_nc == 0) {
     r.decision = KP_DECISION_DELETE;
     r.savings = r.candidate_price;
     return;
   }
-  if (n_nc != 1 || !priced) return;
+  if (n_nc != 1) return;
   const Dict& d = B.d;
   const vector<HostType>& types = cl.catalogs[ci]->types;
   const HostCat& hc = B.cats[ci];
   const bool hasMin = (R->hmin & R->present) != 0;
   if (hasMin) {  // Truncate(reqs, max): minValues must hold on the truncated options, else its pods fail (no-op)
     vector<int> ts(opts, opts + n_opts);
-    if (!HostMinValuesOK(d, hc, *R, ts)) return;
+    if (!HostMinValuesOK(d, hc, *R, ts)) {
+      if (why) {
+        why->n_unscheduled += ws->nc_np;
+        if (ws->nc_pos < ws->bad_pos) why->first_unscheduled = ws->nc_pod;
+      }
+      return exit_as(KP_UNCONS_UNSCHEDULABLE);
+    }
   }
+  if (!all) return exit_as(KP_UNCONS_UNSCHEDULABLE);
   const int kct = d.key(kCapType), bspot = kct >= 0 ? d.bit(kct, "spot") : -1;
   const bool ncSpot = kct < 0 || !((R->present >> kct) & 1) || (bspot >= 0 ? Has(d, *R, kct, bspot) : ((R->compl_ >> kct) & 1));
   const bool s2s = allSpot && ncSpot;  // spot-to-spot: only behind the feature gate
-  if (s2s && !cl.spot_to_spot) return;
   auto worst = [&](int t) {
     return tab ? tab->Worst(d, *R, types[t], tab->off[ci][t], s2s) : WorstLaunch(d, *R, types[t], s2s);
   };
+  if (why) {
+    why->n_truncated = n_opts;
+    double lo = std::numeric_limits<double>::max();
+    for (uint32_t i = 0; i < n_opts; i++) lo = std::min(lo, worst((int)opts[i]));
+    why->cheapest_launch = n_opts ? lo : 0;
+  }
+  if (!priced) {
+    if (why) why->unpriced = unpriced;
+    return exit_as(KP_UNCONS_UNPRICED);
+  }
+  if (s2s && !cl.spot_to_spot) return exit_as(KP_UNCONS_SPOT_TO_SPOT_DISABLED);
   vector<int> kept;
   for (uint32_t i = 0; i < n_opts; i++)
     if (worst((int)opts[i]) < candPrice) kept.push_back((int)opts[i]);
-  if (hasMin && !HostMinValuesOK(d, hc, *R, kept)) return;
-  if (kept.empty()) return;
+  if (why) why->n_cheaper = (uint32_t)kept.size();
+  if (kept.empty()) return exit_as(KP_UNCONS_NOT_CHEAPER);
+  if (hasMin && !HostMinValuesOK(d, hc, *R, kept)) return exit_as(KP_UNCONS_MIN_VALUES, 1);
+  if (why && !multi_node) why->n_same_type = (uint32_t)kept.size();
   if (multi_node) {  // filterOutSameType: the candidates' cheapest price per type name
     vector<std::pair<const string*, double>> prices;
     for (uint32_t c : cand) {
@@ -5822,12 +5872,13 @@ static void GeneralDecide(const kp_cluster& cl, const vector<std::map<string, st
     vector<int> k2;
     for (int t : kept)
       if (worst(t) < maxPrice) k2.push_back(t);
-    if (hasMin && !HostMinValuesOK(d, hc, *R, k2)) return;
+    if (why) why->n_same_type = (uint32_t)k2.size();
+    if (k2.empty()) return exit_as(KP_UNCONS_SAME_TYPE);
+    if (hasMin && !HostMinValuesOK(d, hc, *R, k2)) return exit_as(KP_UNCONS_MIN_VALUES, 2);
     kept.swap(k2);
-    if (kept.empty()) return;
   }
   if (s2s && cand.size() == 1) {
-    if (kept.size() < 15) return;
+    if (kept.size() < 15) return exit_as(KP_UNCONS_SPOT_FLEXIBILITY);
     kept.resize(std::min<size_t>(kept.size(), hasMin ? 100 : 15));
   }
   double best = std::numeric_limits<double>::max();
@@ -5991,7 +6042,8 @@ static void CutToCommand(const Dict& d, kp_solve_result& res, const vector<int>&
 // command (kp_cluster_command): where to leave the decision's command; its placements are already in the simulation's
 // input order and name the Solve's existing nodes
 static int32_t GeneralSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand, const vector<std::map<string, string>>& labels,
-                             int32_t multi_node, SimOut& r, GenTotals& T, kp_cancel* cancel, kp_solve_result** command) {
+                             int32_t multi_node, SimOut& r, GenTotals& T, kp_cancel* cancel, kp_solve_result** command,
+                             kp_sim_why* why = nullptr) {
   SimOneSolve so;
   if (int32_t rc = GeneralSolveOne(plan, cand, so, T, cancel)) return rc;
   const kp_cluster& cl = plan->cluster()->cl;
@@ -6003,10 +6055,21 @@ static int32_t GeneralSimOne(kp_cluster_plan* plan, const vector<uint32_t>& cand
   const int n_nc = (int)res->ncs.size();
   vector<int> kept;
   bool s2s = false;
+  WhySolve ws;
+  if (why) {  // the Solve's fields, from its own result in its own queue order (kp_drift_result's rule)
+    WhyClear(why);
+    ws.why = why;
+    why->n_nodeclaims = (uint32_t)std::min(n_nc, 2);
+    for (int32_t p : so.sp->cp->queue)
+      if (PodUnscheduled(so.kind[p], res->placement[p], [&](int pos) { return so.ex[(size_t)pos].initialized != 0; }))
+        if (why->n_unscheduled++ == 0) why->first_unscheduled = (int32_t)so.cluster_pod[p];
+    // (kp_solve_run has applied Truncate's minValues check: the pods of a NodeClaim that broke it are unplaced already)
+  }
   // (kp_solve_run already applied the held reservations and the minValues truncation check to NodeClaim 0)
   GeneralDecide(cl, labels, cand, *so.sp->cp->B, all, n_nc, n_nc ? &res->fin[0] : nullptr, n_nc ? res->nc_cat[0] : 0,
                 n_nc ? res->ncs[0].nodepool : 0, n_nc ? res->ncs[0].options.data() : nullptr,
-                n_nc ? (uint32_t)res->ncs[0].options.size() : 0, multi_node, r, nullptr, nullptr, &kept, &s2s);
+                n_nc ? (uint32_t)res->ncs[0].options.size() : 0, multi_node, r, nullptr, nullptr, &kept, &s2s,
+                why ? &ws : nullptr);
   if (command && r.decision != KP_DECISION_NOOP) {
     if (r.decision == KP_DECISION_REPLACE) CutToCommand(so.sp->cp->B->d, *so.res, kept, s2s);
     *command = so.res.release();
@@ -6543,9 +6606,10 @@ struct ConsolidateMode final : GeneralMode {
   int32_t multi_node;
   vector<SimOut>& outs;
   kp_solve_result** commands;
+  kp_sim_why* whys;  // kp_cluster_simulate_explained (or null): the reason record of every subset
   ConsolidateMode(kp_cluster_plan* p, GenTotals& t, kp_cancel* c, const vector<std::map<string, string>>& l, int32_t mn,
-                  vector<SimOut>& o, kp_solve_result** cmds)
-      : GeneralMode(p, t, c, 2), labels(l), multi_node(mn), outs(o), commands(cmds) {}  // (a second NodeClaim: no-op)
+                  vector<SimOut>& o, kp_solve_result** cmds, kp_sim_why* w = nullptr)
+      : GeneralMode(p, t, c, 2), labels(l), multi_node(mn), outs(o), commands(cmds), whys(w) {}  // (a second NodeClaim: no-op)
   hipError_t Reserve(const GenRun& R, GenSlot& sl) override {
     const hipError_t e = sl.up.reserve(R.u_end);
     return e != hipSuccess ? e : sl.down.reserve(R.r_end);
@@ -6619,8 +6683,24 @@ struct ConsolidateMode final : GeneralMode {
         np = (uint32_t)C.B->tmpl_nodepool[nct[j]];
       }
       bool s2s = false;
+      WhySolve ws;
+      if (whys) {  // the Solve's fields from the downloaded placements, queue positions ascending (scan_unscheduled's rule)
+        kp_sim_why* w = ws.why = &whys[i];
+        WhyClear(w);
+        w->n_nodeclaims = (uint32_t)std::min(n_nc, 2);
+        for (size_t p = 0; p < q.size(); p++) {
+          const int kind = gb.pod_kind[q[p]];
+          const int32_t pl = place[(size_t)j * Pc + p];
+          if (PodUnscheduled(kind, pl, [&](int pos) { return cl.nodes[gb.pos_node[pos]].node.initialized != 0; })) {
+            if (w->n_unscheduled++ == 0) w->first_unscheduled = gb.pod_cluster[q[p]], ws.bad_pos = (int64_t)p;
+          } else if (kind != 2 && pl >= 0) {
+            if (ws.nc_np++ == 0) ws.nc_pod = gb.pod_cluster[q[p]], ws.nc_pos = (int64_t)p;
+          }
+        }
+      }
       GeneralDecide(cl, labels, R.cands[i], *C.B, all, n_nc, &Rq, ci, np, &opts[(size_t)j * gb.opt_stride],
-                    n_nc == 1 ? nopt[j] : 0, multi_node, out, &gb.offers, &gb.cands, commands ? &keptv[j] : nullptr, &s2s);
+                    n_nc == 1 ? nopt[j] : 0, multi_node, out, &gb.offers, &gb.cands, commands ? &keptv[j] : nullptr, &s2s,
+                    whys ? &ws : nullptr);
       if (commands) s2sv[j] = s2s ? 1 : 0;
     }
     });
@@ -6648,7 +6728,8 @@ struct ConsolidateMode final : GeneralMode {
     return KP_OK;
   }
   int32_t SimOne(const vector<uint32_t>& cand, int s) override {
-    return GeneralSimOne(plan, cand, labels, multi_node, outs[s], T, cancel, commands ? &commands[s] : nullptr);
+    return GeneralSimOne(plan, cand, labels, multi_node, outs[s], T, cancel, commands ? &commands[s] : nullptr,
+                         whys ? &whys[s] : nullptr);
   }
 };
 
@@ -7248,15 +7329,11 @@ static int32_t GeneralPartition(kp_cluster_plan* plan, const uint32_t* offsets, 
   return KP_OK;
 }
 
-static int32_t GeneralSimLocked(kp_cluster_plan* plan, const uint32_t* offsets, const uint32_t* nodes,
-                                uint32_t n_subsets, int32_t multi_node, SimArgs& a, kp_cancel* cancel, BudgetGate* bg,
-                                kp_solve_result** commands = nullptr) {
-  kp_ctx* ctx = plan->ctx;
-  const kp_cluster& cl = plan->general->cl;
+// the nodes' labels as NodeCandidatePrice reads them, built once per plan
+static const vector<std::map<string, string>>& PlanLabels(kp_cluster_plan* plan) {
+  const kp_cluster& cl = plan->cluster()->cl;
   const int N = (int)cl.n_nodes;
-  using clk = std::chrono::steady_clock;
-  const auto t0 = clk::now();
-  vector<std::map<string, string>>& labels = plan->general_labels;  // the nodes' labels (NodeCandidatePrice), once
+  vector<std::map<string, string>>& labels = plan->general_labels;
   if ((int)labels.size() != N) {
     labels.assign(N, {});
     for (int i = 0; i < N; i++)
@@ -7265,16 +7342,31 @@ static int32_t GeneralSimLocked(kp_cluster_plan* plan, const uint32_t* offsets, 
         labels[i][Normalize(l.key ? l.key : "")] = l.value ? l.value : "";
       }
   }
+  return labels;
+}
+// whys (kp_cluster_simulate_explained, or null): [n_subsets] reason records, the budget-blocked subsets' included
+static int32_t GeneralSimLocked(kp_cluster_plan* plan, const uint32_t* offsets, const uint32_t* nodes,
+                                uint32_t n_subsets, int32_t multi_node, SimArgs& a, kp_cancel* cancel, BudgetGate* bg,
+                                kp_solve_result** commands = nullptr, kp_sim_why* whys = nullptr) {
+  kp_ctx* ctx = plan->ctx;
+  using clk = std::chrono::steady_clock;
+  const auto t0 = clk::now();
+  const vector<std::map<string, string>>& labels = PlanLabels(plan);
   vector<vector<uint32_t>> cands;
   vector<int> batched, single;
-  if (int32_t rc = GeneralPartition(plan, offsets, nodes, n_subsets, bg, false, cands, batched, single)) return rc;
+  vector<char> blocked;
+  if (int32_t rc = GeneralPartition(plan, offsets, nodes, n_subsets, bg, false, cands, batched, single, &blocked)) return rc;
+  for (uint32_t s = 0; whys && s < n_subsets; s++) {
+    WhyClear(&whys[s]);
+    if (blocked[s]) whys[s].reason = KP_UNCONS_BUDGET;
+  }
   const double t_setup = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
   vector<SimOut> outs(n_subsets);
   memset(outs.data(), 0, sizeof(SimOut) * outs.size());
   GenTotals T;
   T.batched = batched.size(), T.single = single.size();
   memset(plan->general_phase, 0, sizeof plan->general_phase);
-  ConsolidateMode mode(plan, T, cancel, labels, multi_node, outs, commands);
+  ConsolidateMode mode(plan, T, cancel, labels, multi_node, outs, commands, whys);
   const auto t1 = clk::now();
   if (!batched.empty())
     if (int32_t rc = GeneralBatchRun(*plan->gb, cands, batched, mode)) return rc;
@@ -7399,9 +7491,17 @@ struct ValCheck {
   const uint8_t* val = nullptr;   // device: [n_subsets] ValOut
   const uint8_t* gate = nullptr;  // device: [n_subsets] 1 admissible, 0 blocked (budgets only)
 };
+// kp_cluster_simulate_explained on a plan of the batched kernel: where the launch leaves the reason records and their
+// histogram (why_count_kernel, which also writes the budget-blocked subsets' records)
+struct WhyEmit {
+  const uint8_t* rec = nullptr;     // device: [n_subsets] WhyOut
+  const uint64_t* counts = nullptr; // device: [KP_UNCONS_COUNT]
+  kp_sim_why* host = nullptr;       // general-path plans: the caller's records, filled by the decision code
+};
+static_assert(sizeof(WhyOut) == sizeof(kp_sim_why) && WHY_REASONS == KP_UNCONS_COUNT, "WhyOut mirrors kp_sim_why");
 static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, const uint32_t* nodes, uint32_t n_subsets,
                                int32_t multi_node, SimArgs& a_out, kp_cancel* cancel, BudgetGate* bg = nullptr,
-                               CmdEmit* em = nullptr, ValCheck* vc = nullptr) {
+                               CmdEmit* em = nullptr, ValCheck* vc = nullptr, WhyEmit* wy = nullptr) {
   kp_ctx* ctx = plan->ctx;
   if (cancel && __atomic_load_n(cancel->flag, __ATOMIC_SEQ_CST))
     return fail(KP_E_CANCELED, "cancelled before the simulations");
@@ -7410,7 +7510,8 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
     bg->blocked = 0;
   }
   if (plan->general)
-    return GeneralSimLocked(plan, offsets, nodes, n_subsets, multi_node, a_out, cancel, bg, em ? em->commands : nullptr);
+    return GeneralSimLocked(plan, offsets, nodes, n_subsets, multi_node, a_out, cancel, bg, em ? em->commands : nullptr,
+                            wy ? wy->host : nullptr);
   if (int32_t rc = CatalogsAlive(plan->cp->B->alive)) return rc;
   if (SeqnumsOf(plan->cp->B->catalogs) != plan->cp->B->seqnums)
     return fail(KP_E_INVAL, "stale plan: a catalogue's seqnum changed since it was prepared (kp_cluster_refresh)");
@@ -7447,7 +7548,10 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
     a.cancel = (const int32_t*)dp;
   }
   hipFuncAttributes fa;
-  HIPCHK(hipFuncGetAttributes(&fa, vc ? sim_check_kernel_ptr() : em ? sim_emit_kernel_ptr() : sim_kernel_ptr(bg != nullptr)));
+  HIPCHK(hipFuncGetAttributes(&fa, wy   ? sim_why_kernel_ptr()
+                                   : vc ? sim_check_kernel_ptr()
+                                   : em ? sim_emit_kernel_ptr()
+                                        : sim_kernel_ptr(bg != nullptr)));
   const size_t lds_wg = fa.sharedSizeBytes + (size_t)SIM_WAVES * a.wave_lds;
   if (lds_wg > 160 * 1024) return fail(KP_E_UNSUPPORTED, "simulation LDS %zu B per workgroup (cluster or subsets too large)", lds_wg);
   const int wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds_wg));
@@ -7495,7 +7599,7 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
   const size_t b_out = al(sizeof(SimOut) * n_subsets);
   // the budget gate's regions: gate bytes, live list, block counts and offsets, allowed[], the live count
   const uint32_t n_gblk = (n_subsets + GATE_BLOCK - 1) / GATE_BLOCK;
-  const size_t g_gate = bg ? al(n_subsets) : 0, g_live = bg || em || vc ? al(sizeof(uint32_t) * n_subsets) : 0;
+  const size_t g_gate = bg ? al(n_subsets) : 0, g_live = bg || em || vc || wy ? al(sizeof(uint32_t) * n_subsets) : 0;
   const size_t g_blk = bg ? al(sizeof(uint32_t) * n_gblk) : 0, g_allowed = bg ? al(sizeof(uint32_t) * (plan->n_pools + 1)) : 0;
   // the command records (kp_cluster_command), sized from the batch: behind everything else
   const size_t o_rec = b_off + b_nodes + b_out + g_gate + g_live + 2 * g_blk + g_allowed + (bg ? 256 : 0);
@@ -7509,7 +7613,11 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
   const size_t o_chk = o_rec + al(rec_stride * n_subsets);
   const size_t v_want = vc ? al(sizeof(uint64_t) * vc->want.size()) : 0, v_unk = vc ? al(sizeof(uint32_t) * vc->unknown.size()) : 0;
   const size_t v_rep = vc ? al(n_subsets) : 0, v_val = vc ? al(sizeof(ValOut) * n_subsets) : 0;
-  const size_t b_total = o_chk + v_want + v_unk + v_rep + v_val;
+  // the reason records, the histogram's partials and the histogram (kp_cluster_simulate_explained): behind those
+  const size_t o_why = o_chk + v_want + v_unk + v_rep + v_val;
+  const size_t y_rec = wy ? al(sizeof(WhyOut) * n_subsets) : 0;
+  const size_t y_part = wy ? al(sizeof(uint64_t) * WHY_REASONS * WHY_COUNT_MAX_BLOCKS) : 0;
+  const size_t b_total = o_why + y_rec + y_part + (wy ? al(sizeof(uint64_t) * WHY_REASONS) : 0);
   if (b_total > plan->batch_bytes) {
     if (plan->batch.p) HIPCHK(hipFree(plan->batch.p));
     plan->batch.p = nullptr;
@@ -7540,6 +7648,13 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
     em->rec = bb + o_rec;
     em->stride = rec_stride;
     em->cap = cap;
+  }
+  SimWhy sw{nullptr, (uint32_t*)(bb + o_why)};
+  uint64_t* why_part = (uint64_t*)(bb + o_why + y_rec);
+  uint64_t* why_counts = (uint64_t*)(bb + o_why + y_rec + y_part);
+  if (wy) {
+    wy->rec = bb + o_why;
+    wy->counts = why_counts;
   }
   if (bg) {
     // the gate on the resident batch, then the live count (4 bytes) sizes the simulation grid
@@ -7572,15 +7687,18 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
     plan->sim_waves[0] = n_live ? (uint64_t)a.n_slots : 0;  // (no live subset: nothing is launched)
     plan->sim_waves[1] = (n_live + (uint32_t)a.n_slots - 1) / (uint32_t)a.n_slots;
     HIPCHK(hipEventRecord(ctx->ev0, st));
-    se.live = sc.live = g.live;
+    se.live = sc.live = sw.live = g.live;
     if (vc) vc->gate = g.gate;
-    if (n_live && vc) HIPCHK(launch_sim_check(a, sc, (int)n_live, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
+    if (wy) {
+      if (n_live) HIPCHK(launch_sim_why(a, sw, (int)n_live, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
+      HIPCHK(launch_why_count(sw.rec, g.gate, (int)n_subsets, why_part, why_counts, st));
+    } else if (n_live && vc) HIPCHK(launch_sim_check(a, sc, (int)n_live, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
     else if (n_live && em) HIPCHK(launch_sim_emit(a, se, (int)n_live, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
     else if (n_live) HIPCHK(launch_sim_gated(a, g.live, (int)n_live, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
     HIPCHK(hipEventRecord(ctx->ev1, st));
     return KP_OK;
   }
-  if (em || vc) {
+  if (em || vc || wy) {
     // No budgets: the emitting (and the checking) instantiation walks every subset, in order, through an identity list. An ungated
     // emitting policy would be a fourth sim_kernel instantiation (its own code object and resource figures to hold)
     // to save one 4 * n_subsets byte upload on a call made for a few subsets.
@@ -7588,9 +7706,12 @@ static int32_t SimLaunchLocked(kp_cluster_plan* plan, const uint32_t* offsets, c
     plan->cmd_live.resize(n_subsets);
     for (uint32_t s = 0; s < n_subsets; s++) plan->cmd_live[s] = s;
     HIPCHK(hipMemcpyAsync(live, plan->cmd_live.data(), sizeof(uint32_t) * n_subsets, hipMemcpyHostToDevice, st));
-    se.live = sc.live = live;
+    se.live = sc.live = sw.live = live;
     HIPCHK(hipEventRecord(ctx->ev0, st));
-    if (vc) HIPCHK(launch_sim_check(a, sc, (int)n_subsets, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
+    if (wy) {
+      HIPCHK(launch_sim_why(a, sw, (int)n_subsets, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
+      HIPCHK(launch_why_count(sw.rec, nullptr, (int)n_subsets, why_part, why_counts, st));
+    } else if (vc) HIPCHK(launch_sim_check(a, sc, (int)n_subsets, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
     else HIPCHK(launch_sim_emit(a, se, (int)n_subsets, blocks, (size_t)SIM_WAVES * a.wave_lds, st));
     HIPCHK(hipEventRecord(ctx->ev1, st));
     return KP_OK;
@@ -7763,6 +7884,99 @@ int32_t kp_cluster_command(kp_cluster_plan* plan, kp_cancel* cancel, const uint3
     return rc;
   }
   if (n_blocked && allowed) *n_blocked = bg.blocked;
+  return KP_OK;
+}
+
+// ---- Why a subset cannot be consolidated (kp_cluster_simulate_explained) ------------------------------------------
+int32_t kp_cluster_simulate_explained(kp_cluster_plan* plan, kp_cancel* cancel, const uint32_t* offsets,
+                                      const uint32_t* nodes, uint32_t n_subsets, int32_t multi_node,
+                                      const uint32_t* allowed, uint32_t n_allowed, kp_sim_result* out, kp_sim_why* why,
+                                      uint64_t* counts, uint64_t* n_blocked, kp_solve_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (n_blocked) *n_blocked = 0;
+  if (counts) memset(counts, 0, sizeof(uint64_t) * KP_UNCONS_COUNT);
+  if (!plan || (n_subsets && (!offsets || !out || (!why && !counts)))) return fail(KP_E_INVAL, "null argument");
+  if (cancel && cancel->ctx.p != plan->ctx.p) return fail(KP_E_INVAL, "the cancel token belongs to another context");
+  kp_ctx* ctx = plan->ctx;
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  HIPCHK(hipSetDevice(ctx->device));
+  if (stats) memset(stats, 0, sizeof *stats);
+  BudgetGate gate{allowed, n_allowed};
+  BudgetGate* bg = allowed ? &gate : nullptr;
+  if (bg)
+    if (int32_t rc = CheckBudget(plan, bg)) return rc;
+  if (n_subsets == 0) return KP_OK;
+  // why == NULL: the histogram alone. The records then stay on the device, unless the host needs them: a general-path
+  // plan fills them on the host, and with NodePool limits the MULTIPLE_NODECLAIMS ones are settled below.
+  bool limited = false;
+  if (!plan->general)
+    for (uint32_t lp : plan->cp->tmpl_limit_present) limited = limited || lp != 0;
+  vector<kp_sim_why> own;
+  if (!why && (plan->general || limited)) {
+    own.resize(n_subsets);
+    why = own.data();
+  }
+  SimArgs a;
+  WhyEmit wy;
+  wy.host = why;
+  if (int32_t rc = SimLaunchLocked(plan, offsets, nodes, n_subsets, multi_node, a, cancel, bg, nullptr, nullptr, &wy)) return rc;
+  hipStream_t st = ctx->stream;
+  uint64_t kst[8];
+  uint64_t hist[KP_UNCONS_COUNT] = {};
+  HIPCHK(hipMemcpyAsync(out, a.out, sizeof(SimOut) * n_subsets, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(kst, a.stats, sizeof kst, hipMemcpyDeviceToHost, st));
+  if (!plan->general) {
+    if (why) HIPCHK(hipMemcpyAsync(why, wy.rec, sizeof(WhyOut) * n_subsets, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hist, wy.counts, sizeof hist, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  if (!plan->general && kst[5]) return fail(KP_E_CANCELED, "consolidation simulations cancelled (kp_cancel_set)");
+  float ms = (float)plan->general_ms;
+  if (!plan->general) HIPCHK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  for (uint32_t s = 0; s < n_subsets; s++)
+    if (out[s].n_pods == 0xFFFFFFFFu) return fail(KP_E_DEVICE, "subset %u overflowed the pod queue", s);
+  GenTotals T = TotalsOf(kst, ms);
+  uint64_t reruns = 0;
+  if (plan->general) {
+    for (uint32_t s = 0; s < n_subsets; s++)
+      if ((uint32_t)why[s].reason < KP_UNCONS_COUNT) hist[why[s].reason]++;
+  } else {
+    // NodePool limits: sim_kernel stops where a pod would open a second NodeClaim, judged by the limits the pass began
+    // with, while the first NodeClaim has taken its largest option out of its pool's remaining limits (subtractMax): that
+    // second NodeClaim may not exist and the pod fail instead. MULTIPLE_NODECLAIMS against UNSCHEDULABLE is this call's
+    // answer, so every such record is settled by the subset's own whole Solve and the decision code's reasons (as
+    // kp_cluster_validate settles its rule 3). out[s] stays the kernel's: a Solve that would change it (a pending pod
+    // was the one without a second NodeClaim) leaves the kernel's record too.
+    if (limited) {
+      if (!plan->cluster()) return fail(KP_E_INVAL, "the plan keeps no cluster");
+      const vector<std::map<string, string>>& labels = PlanLabels(plan);
+      for (uint32_t s = 0; s < n_subsets; s++) {
+        if (why[s].reason != KP_UNCONS_MULTIPLE_NODECLAIMS) continue;
+        const vector<uint32_t> cand(nodes + offsets[s], nodes + offsets[s + 1]);
+        SimOut r;
+        memset(&r, 0, sizeof r);
+        kp_sim_why w;
+        if (int32_t rc = GeneralSimOne(plan, cand, labels, multi_node, r, T, cancel, nullptr, &w)) return rc;
+        reruns++;
+        if (r.decision != out[s].decision || (uint32_t)w.reason >= KP_UNCONS_COUNT) continue;
+        hist[KP_UNCONS_MULTIPLE_NODECLAIMS]--;
+        hist[w.reason]++;
+        why[s] = w;
+      }
+    }
+  }
+  if (counts) memcpy(counts, hist, sizeof hist);
+  if (n_blocked && bg) *n_blocked = gate.blocked;
+  if (stats) {
+    FillStats(stats, plan, T, t0);
+    if (plan->general) {
+      for (int k = 0; k < 8; k++) stats->attempt_cycles[k] = plan->general_phase[k];  // (timing diagnostics)
+    } else {  // batched sweep: wave slots launched, most subsets any wave ran, subsets settled by their own Solve
+      stats->phase_cycles[1] = plan->sim_waves[0];
+      stats->phase_cycles[2] = plan->sim_waves[1];
+      stats->phase_cycles[3] = reruns;
+    }
+  }
   return KP_OK;
 }
 

@@ -272,6 +272,11 @@ __global__ __launch_bounds__(SIM_WAVES * 64) void sim_prep_kernel(SimArgs a) {
 // GL::gated fold away before code generation, so that instantiation compiles as it did without the gate.
 // GL = SimCheck (kp_cluster_validate) is gated too and takes no decision: every statement of its own sits under
 // GL::check, which is false in the three other policies, so those are generated from the code they had.
+// GL = SimWhy (kp_cluster_simulate_explained) is gated, decides as SimLive decides and also says which exit a no-op
+// took (kp_abi.h's order): every statement of its own sits under GL::why, false in the four other policies. It runs a
+// simulation to its end as SimCheck does, truncates before it looks at the prices and the spot-to-spot gate (the other
+// deciding policies test the gate first: both are no-ops there), and the price stages then run only for a simulation
+// SimLive would have taken that far.
 template <int NW, class GL>
 __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, GL gl) {
   __shared__ DevDict D;
@@ -366,15 +371,20 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
     }
     double candPrice = 0;
     int flags_and = 3;
+    int w_unpriced = -1;  // GL::why: the first candidate without a label-compatible offering (position in S)
     if (lane == 0) {  // getCandidatePrices: summed in candidate order (float addition order matters)
       for (int i = 0; i < ns; i++) {
         const uint32_t c = a.sub_nodes[s0 + i];
         candPrice += a.node_price[c];
         flags_and &= a.node_flags[c];
+        if constexpr (GL::why) {
+          if (w_unpriced < 0 && !(a.node_flags[c] & 1)) w_unpriced = i;
+        }
       }
     }
     candPrice = lane_bcast_f64(candPrice, 0);
     flags_and = __builtin_amdgcn_readlane(flags_and, 0);
+    if constexpr (GL::why) w_unpriced = __builtin_amdgcn_readlane(w_unpriced, 0);
     const bool priced = flags_and & 1, allSpot = (flags_and >> 1) & 1;
     int n2 = 1;
     while (n2 < n) n2 <<= 1;
@@ -419,6 +429,9 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
     // whether the simulation stopped at a second NodeClaim
     int n_uninit = 0, nc_np = 0;
     bool multi = false;
+    // GL::why counts those too, and keeps the lowest queue position of a candidate pod on an uninitialized node and of
+    // a non-pending pod on the NodeClaim (the first unscheduled pod, should its truncated options break minValues)
+    int w_uninit_first = 0x7FFFFFFF, w_nc_first = 0x7FFFFFFF;
     while (len > 0) {
       const int i = ring[head];
       const uint64_t ent = spod[i];
@@ -483,7 +496,13 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
         if constexpr (GL::check) {  // the verdict counts it with the unscheduled pods; the Solve goes on
           if (!a.ex_init[e] && kind == 0) n_uninit++;
         }
-        if (!GL::check && !a.ex_init[e] && kind == 0) {
+        if constexpr (GL::why) {
+          if (!a.ex_init[e] && kind == 0) {
+            n_uninit++;
+            w_uninit_first = min(w_uninit_first, i);
+          }
+        }
+        if (!GL::check && !GL::why && !a.ex_init[e] && kind == 0) {
           abort = true;  // SimulateScheduling: a candidate pod relied on an uninitialized node
         } else {
           const bool first = !((dirty[e >> 6] >> (e & 63)) & 1);
@@ -543,7 +562,7 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
       if (placed == -1 && a.tres[sl].tmpl >= 0) {
         if (n_nc == 1) {
           abort = true;
-          if constexpr (GL::check) multi = true;
+          if constexpr (GL::check || GL::why) multi = true;
         } else {
           copy_u64(reinterpret_cast<uint64_t*>(nc), reinterpret_cast<const uint64_t*>(&a.tres[sl]),
                    (int)(sizeof(SimNC) / 8));
@@ -559,6 +578,12 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
         if (kind != 2) placed_cnt++;
         if constexpr (GL::check) {
           if (placed == 0 && kind != 2) nc_np++;
+        }
+        if constexpr (GL::why) {
+          if (placed == 0 && kind != 2) {
+            nc_np++;
+            w_nc_first = min(w_nc_first, i);
+          }
         }
         if constexpr (GL::emit) {  // where the pod went, and the NodeClaim's add order
           if (lane == 0) {
@@ -587,6 +612,28 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
       }
     }
 
+    // GL::why: the first unscheduled pod in queue order, as cluster pod indices, before the option sort reuses keys[].
+    // The pods never placed are what the ring still holds (len entries from head); w_pod_bad is the first of those and
+    // of the candidate pods on uninitialized nodes, w_pod_nc the first non-pending pod on the NodeClaim.
+    int w_pos_bad = 0x7FFFFFFF, w_pod_bad = -1, w_pod_nc = -1;
+    if constexpr (GL::why) {
+      if (!abort) {
+        int mine = w_uninit_first;
+        for (int k = lane; k < len; k += 64) {
+          int at = head + k;
+          if (at >= n) at -= n;
+          const int i = ring[at];
+          if (a.pod_kind[a.rank_pod[keys[i]]] != 2) mine = min(mine, i);
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) mine = min(mine, __shfl_xor(mine, o, 64));
+        w_pos_bad = mine;
+        if (w_pos_bad != 0x7FFFFFFF) w_pod_bad = (int)a.rank_pod[keys[w_pos_bad]];
+        if (w_nc_first != 0x7FFFFFFF) w_pod_nc = (int)a.rank_pod[keys[w_nc_first]];
+      }
+      sim_sync();
+    }
+
     // ---- decision (computeConsolidation) ---------------------------------------------------------
     int decision = KP_DECISION_NOOP, nodepool = 0, n_options = 0;
     double repl = 0, savings = 0;
@@ -596,11 +643,18 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
     // spot-to-spot gate say, and no price stage runs.
     bool v_minok = true;
     int v_missing = 0;
-    if (!abort && (GL::check || placed_cnt == need)) {
+    // GL::why: the exit (enum kp_unconsolidatable) and the stage counts; w_sched: every non-pending pod scheduled, none
+    // on an uninitialized node - what takes the other deciding policies past this point
+    const bool w_sched = placed_cnt == need && n_uninit == 0;
+    int w_reason = KP_UNCONS_NONE, w_stage = 0, w_trunc = 0, w_cheaper = 0, w_same = 0;
+    double w_cheapest = 0;
+    if (!abort && (GL::check || GL::why || placed_cnt == need)) {
       if (n_nc == 0) {
-        decision = KP_DECISION_DELETE;
-        savings = candReported;
-      } else if (GL::check || priced) {
+        if (!GL::why || w_sched) {
+          decision = KP_DECISION_DELETE;
+          savings = candReported;
+        }
+      } else if (GL::check || GL::why || priced) {
         const int cat = a.tmpl_catalog[nc->tmpl];
         const DevCatalog& Cg = a.cats[cat];
         const uint64_t v = lane < D.W ? nc->reqs.vals[lane] : 0;
@@ -615,7 +669,7 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
         // spot-to-spot (every candidate spot, the replacement may launch spot): only with the feature gate, on
         // the replacement narrowed to spot offerings, and a single candidate needs 15 cheaper options
         const bool s2s = allSpot && ncSpot;
-        if (GL::check || !s2s || a.spot_to_spot) {
+        if (GL::check || GL::why || !s2s || a.spot_to_spot) {
           // TruncateInstanceTypes: OrderByPrice (cheapest compatible offering, then name) + cut
           const uint64_t Xl = lane < D.TW ? nc->X[lane] : 0;
           int cnt = 0;
@@ -704,6 +758,19 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
                 }
               }
             }
+            if constexpr (GL::why) {
+              // Truncate's verdict is the Solve's (v_minok: a broken list fails the NodeClaim's pods). A scheduled
+              // simulation whose list held reports it and its cheapest worst launch price over both lane halves; the
+              // price stages run only past the candidates' prices and the spot-to-spot gate, in that order.
+              v_minok = ok;
+              if (ok && w_sched) {
+                w_trunc = lim;
+                w_cheapest = wave_min_f64(wlp[0] < wlp[1] ? wlp[0] : wlp[1]);
+                if (!priced) w_reason = KP_UNCONS_UNPRICED;
+                else if (s2s && !a.spot_to_spot) w_reason = KP_UNCONS_SPOT_TO_SPOT_DISABLED;
+              }
+              ok = ok && w_sched && w_reason == KP_UNCONS_NONE;
+            }
             bool keep[2] = {tt[0] >= 0 && wlp[0] < candPrice, tt[1] >= 0 && wlp[1] < candPrice};
             for (int stage = 0; stage < 2 && ok; stage++) {
               if (stage == 1) {
@@ -733,10 +800,20 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
               }
               if (count == 0) ok = false;
               n_options = count;
+              if constexpr (GL::why) {  // an empty set is the filter's exit; minValues only breaks a non-empty one
+                if (stage == 0) w_cheaper = count;
+                else w_same = count;
+                if (count == 0) w_reason = stage == 0 ? KP_UNCONS_NOT_CHEAPER : KP_UNCONS_SAME_TYPE;
+                else if (!ok) w_reason = KP_UNCONS_MIN_VALUES, w_stage = stage + 1;
+              }
+            }
+            if constexpr (GL::why) {
+              if (ok && !a.multi_node) w_same = w_cheaper;  // no same-type filter: the set passes on
             }
             if (ok && s2s && ns == 1) {  // MinInstanceTypesForSpotToSpotConsolidation, then the launch keeps 15
               if (n_options < 15) {
                 ok = false;
+                if constexpr (GL::why) w_reason = KP_UNCONS_SPOT_FLEXIBILITY;
               } else {  // the first 15 (100 with minValues) kept options in price order
                 const int L = hmin ? 100 : 15;
                 const uint64_t lt = (1ull << lane) - 1;
@@ -799,6 +876,38 @@ __global__ __launch_bounds__(NW * 64) SIM_OCCUPANCY void sim_kernel(SimArgs a, G
       for (int k = 0; k < 6; k++) mine = lane == k ? w[k] : mine;
       if (lane < 6) gl.val[(size_t)sub * 6 + lane] = mine;
     }
+    if constexpr (GL::why) {
+      // the record of kp_abi.h (kp_sim_why) from this simulation's own values; every lane holds the same twelve words
+      // and every word is written whatever the exit, so nothing of the slot's previous subset survives
+      uint32_t unsched = 0;
+      int first = -1;
+      if (multi) {
+        w_reason = KP_UNCONS_MULTIPLE_NODECLAIMS;
+      } else if (!overflow) {
+        unsched = (uint32_t)(need - placed_cnt + n_uninit + (v_minok ? 0 : nc_np));
+        first = w_pod_bad;
+        if (!v_minok && w_nc_first < w_pos_bad) first = w_pod_nc;
+        if (unsched || !v_minok) w_reason = KP_UNCONS_UNSCHEDULABLE;
+      }
+      const bool solved = w_reason != KP_UNCONS_MULTIPLE_NODECLAIMS && w_reason != KP_UNCONS_UNSCHEDULABLE;
+      const uint64_t cl = (uint64_t)__double_as_longlong(solved ? w_cheapest : 0.0);
+      const uint32_t w[WHY_WORDS] = {(uint32_t)w_reason,
+                                     (uint32_t)w_stage,
+                                     multi ? 2u : (uint32_t)n_nc,
+                                     unsched,
+                                     (uint32_t)first,
+                                     (uint32_t)(w_reason == KP_UNCONS_UNPRICED ? w_unpriced : -1),
+                                     solved ? (uint32_t)w_trunc : 0u,
+                                     (uint32_t)w_cheaper,
+                                     (uint32_t)w_same,
+                                     0u,
+                                     (uint32_t)cl,
+                                     (uint32_t)(cl >> 32)};
+      uint32_t mine = 0;
+#pragma unroll
+      for (int k = 0; k < WHY_WORDS; k++) mine = lane == k ? w[k] : mine;
+      if (lane < WHY_WORDS) gl.rec[(size_t)gl.live[sim] * WHY_WORDS + lane] = mine;
+    }
     if (!GL::check && lane == 0) {
       SimOut o;
       o.decision = decision;
@@ -860,6 +969,75 @@ hipError_t launch_sim_check(const SimArgs& a, const SimCheck& ck, int n_live, in
   return hipGetLastError();
 }
 const void* sim_check_kernel_ptr() { return reinterpret_cast<const void*>(sim_kernel<SIM_WAVES, SimCheck>); }
+hipError_t launch_sim_why(const SimArgs& a, const SimWhy& wy, int n_live, int blocks, size_t dyn_lds, hipStream_t s) {
+  SimArgs al = a;
+  al.n_subsets = n_live;
+  hipLaunchKernelGGL((sim_kernel<SIM_WAVES, SimWhy>), dim3(blocks), dim3(SIM_WAVES * 64), dyn_lds, s, al, wy);
+  return hipGetLastError();
+}
+const void* sim_why_kernel_ptr() { return reinterpret_cast<const void*>(sim_kernel<SIM_WAVES, SimWhy>); }
+
+// ------------------------------------------------------------------------------------------------
+// The histogram of a batch's reasons (kp_cluster_simulate_explained), so that a sweep is explained without reading its
+// 48-byte records back. Two stages as argmax_kernel's: blocks count contiguous ranges into part[block][reason], one
+// block adds the partials. Integer counts in registers, a shuffle tree per wave and one LDS row per wave: no atomics,
+// and the result does not depend on any order. A subset the budget gate blocked has no simulation: the first stage
+// writes its KP_UNCONS_BUDGET record (one thread, twelve plain stores) and counts it there.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(WHY_COUNT_THREADS) void why_count_kernel(uint32_t* rec, const uint8_t* gate, int n,
+                                                                      uint64_t* part) {
+  __shared__ uint32_t s_cnt[WHY_COUNT_THREADS / 64][WHY_REASONS];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = LANE;
+  const int per = (n + gridDim.x - 1) / gridDim.x;
+  const int lo = blockIdx.x * per, hi = min(n, lo + per);
+  uint32_t c[WHY_REASONS];
+#pragma unroll
+  for (int k = 0; k < WHY_REASONS; k++) c[k] = 0;
+  for (int i = lo + tid; i < hi; i += WHY_COUNT_THREADS) {
+    uint32_t* r = rec + (size_t)i * WHY_WORDS;
+    uint32_t reason;
+    if (gate && !gate[i]) {
+      reason = KP_UNCONS_BUDGET;
+#pragma unroll
+      for (int k = 0; k < WHY_WORDS; k++) r[k] = k == 0 ? (uint32_t)KP_UNCONS_BUDGET : ((k == 4 || k == 5) ? 0xFFFFFFFFu : 0u);
+    } else {
+      reason = r[0];
+    }
+#pragma unroll
+    for (int k = 0; k < WHY_REASONS; k++) c[k] += reason == (uint32_t)k ? 1u : 0u;
+  }
+#pragma unroll
+  for (int k = 0; k < WHY_REASONS; k++) {
+    uint32_t v = c[k];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    if (lane == 0) s_cnt[wave][k] = v;
+  }
+  __syncthreads();
+  if (tid < WHY_REASONS) {
+    uint64_t t = 0;
+    for (int w = 0; w < WHY_COUNT_THREADS / 64; w++) t += s_cnt[w][tid];
+    part[(size_t)blockIdx.x * WHY_REASONS + tid] = t;
+  }
+}
+// one block: thread k adds the partials of reason k, in block order
+__global__ __launch_bounds__(64) void why_count_final_kernel(const uint64_t* part, int np, uint64_t* counts) {
+  const int k = threadIdx.x;
+  if (k >= WHY_REASONS) return;
+  uint64_t t = 0;
+  for (int b = 0; b < np; b++) t += part[(size_t)b * WHY_REASONS + k];
+  counts[k] = t;
+}
+hipError_t launch_why_count(uint32_t* rec, const uint8_t* gate, int n, uint64_t* part, uint64_t* counts, hipStream_t s) {
+  const int nb = why_count_blocks(n);
+  if (n > 0) {
+    hipLaunchKernelGGL(why_count_kernel, dim3(nb), dim3(WHY_COUNT_THREADS), 0, s, rec, gate, n, part);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(why_count_final_kernel, dim3(1), dim3(64), 0, s, part, n > 0 ? nb : 0, counts);
+  return hipGetLastError();
+}
 const void* sim_kernel_ptr(bool gated) {
   return gated ? reinterpret_cast<const void*>(sim_kernel<SIM_WAVES, SimLive>)
                : reinterpret_cast<const void*>(sim_kernel<SIM_WAVES, SimAll>);

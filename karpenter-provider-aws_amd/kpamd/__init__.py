@@ -136,6 +136,9 @@ def load_lib(path=None):
                                             P(C.c_uint64), P(abi.SolveStats)]),
         "kp_cluster_candidates": (C.c_int32, [C.c_void_p, P(abi.CandidatesIn), C.c_void_p, P(C.c_uint32), P(C.c_uint32),
                                               P(abi.SolveStats)]),
+        "kp_cluster_simulate_explained": (C.c_int32, [C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32), C.c_uint32,
+                                                      C.c_int32, P(C.c_uint32), C.c_uint32, P(abi.SimResult),
+                                                      P(abi.SimWhy), P(C.c_uint64), P(C.c_uint64), P(abi.SolveStats)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name, None)
@@ -829,6 +832,30 @@ class ClusterPlan:
         if allowed is not None:
             sd["budget_blocked"] = int(blocked.value)
         return [{f: int(getattr(out[i], f)) for f, _ in abi.Validation._fields_} for i in range(n)], sd
+
+    def simulate_explained(self, subsets, multi_node=True, allowed=None, cancel=None, records=True):
+        """kp_cluster_simulate_explained: simulate() plus, per subset, which exit of computeConsolidation made it a
+        no-op. Returns (sims, whys, counts, stats): sims as simulate() gives them (bit for bit kp_cluster_simulate_budgeted's),
+        whys the kp_sim_why dicts (reason: abi.UNCONS_*), counts the abi.UNCONS_COUNT-entry histogram of the reasons;
+        stats gain budget_blocked when allowed is given. records=False passes why = NULL: whys is None and only the
+        histogram is read back."""
+        lib = self.ctx.lib
+        arena = Arena()
+        offs, flat = abi.subsets_csr(arena, subsets)
+        n = len(subsets)
+        out = (abi.SimResult * max(1, n))()
+        why = (abi.SimWhy * max(1, n))() if records else None
+        counts = (C.c_uint64 * abi.UNCONS_COUNT)()
+        blocked, st = C.c_uint64(0), abi.SolveStats()
+        keep, ap, na = self._allowed(allowed) if allowed is not None else (None, None, 0)
+        _check(lib, lib.kp_cluster_simulate_explained(self.h, cancel.h if cancel is not None else None, offs, flat, n,
+                                                      1 if multi_node else 0, ap, na, out, why, counts, C.byref(blocked),
+                                                      C.byref(st)))
+        sd = stats_dict(st)
+        if allowed is not None:
+            sd["budget_blocked"] = int(blocked.value)
+        return ([sim_dict(out[i]) for i in range(n)], [abi.why_dict(why[i]) for i in range(n)] if records else None,
+                [int(c) for c in counts], sd)
 
     def candidates(self, method, now, controls=None):
         """kp_cluster_candidates for one method (abi.METHOD_*) at unix time now, on controls (default: the cluster's

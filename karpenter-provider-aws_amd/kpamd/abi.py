@@ -384,6 +384,29 @@ VALIDITY_NAMES = ("KP_VALID", "KP_INVALID_UNSCHEDULED", "KP_INVALID_NO_REPLACEME
 DECISION_DELETE, DECISION_REPLACE = 1, 2
 
 
+class SimWhy(C.Structure):
+    """kp_sim_why: which exit of computeConsolidation a simulation took (kp_cluster_simulate_explained)."""
+    _fields_ = [("reason", C.c_int32), ("stage", C.c_int32), ("n_nodeclaims", C.c_uint32), ("n_unscheduled", C.c_uint32),
+                ("first_unscheduled", C.c_int32), ("unpriced", C.c_int32), ("n_truncated", C.c_uint32),
+                ("n_cheaper", C.c_uint32), ("n_same_type", C.c_uint32), ("reserved_", C.c_uint32),
+                ("cheapest_launch", C.c_double)]
+
+
+(UNCONS_NONE, UNCONS_BUDGET, UNCONS_MULTIPLE_NODECLAIMS, UNCONS_UNSCHEDULABLE, UNCONS_UNPRICED,
+ UNCONS_SPOT_TO_SPOT_DISABLED, UNCONS_NOT_CHEAPER, UNCONS_SAME_TYPE, UNCONS_SPOT_FLEXIBILITY, UNCONS_MIN_VALUES) = range(10)
+UNCONS_COUNT = 10
+UNCONS_NAMES = ("KP_UNCONS_NONE", "KP_UNCONS_BUDGET", "KP_UNCONS_MULTIPLE_NODECLAIMS", "KP_UNCONS_UNSCHEDULABLE",
+                "KP_UNCONS_UNPRICED", "KP_UNCONS_SPOT_TO_SPOT_DISABLED", "KP_UNCONS_NOT_CHEAPER", "KP_UNCONS_SAME_TYPE",
+                "KP_UNCONS_SPOT_FLEXIBILITY", "KP_UNCONS_MIN_VALUES")
+WHY_FIELDS = ("reason", "stage", "n_nodeclaims", "n_unscheduled", "first_unscheduled", "unpriced", "n_truncated",
+              "n_cheaper", "n_same_type", "cheapest_launch")
+
+
+def why_dict(w):
+    """kp_sim_why -> dict (reserved_ left out; cheapest_launch a float, the rest ints)."""
+    return {f: (float(w.cheapest_launch) if f == "cheapest_launch" else int(getattr(w, f))) for f in WHY_FIELDS}
+
+
 class Choice(C.Structure):
     """kp_choice: the sweep's best decision over all ranks (kp_consolidate_argmin / kp_choice_reduce)."""
     _fields_ = [("subset", C.c_int64), ("counts", C.c_uint64 * 3), ("overflowed", C.c_uint64), ("result", SimResult)]

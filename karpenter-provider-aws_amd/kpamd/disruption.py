@@ -35,6 +35,10 @@ CS3 and R:website/content/en/preview/concepts/disruption.md:89-128):
                                             node name (gone, deleting, nominated, the budget walk), then one
                                             plan.validate (kp_cluster_validate) of the command's decision and options.
                                             Nothing validates unless asked; Drift commands are not validated.
+  unconsolidatable(cluster, plan, now)      why each managed node stays, for the single-node pass: the candidate reason
+  unconsolidatable_message(entry)           where it is no candidate, else the exit of its singleton's simulation
+                                            (plan.simulate_explained, kp_cluster_simulate_explained) under the budget
+                                            walk; the message renders the Unconsolidatable event's text
 
 NodePool disruption budgets (R:website/content/en/preview/concepts/disruption.md:274-333,
 R:pkg/apis/crds/karpenter.sh_nodepools.yaml:95-135), modelled when a NodePool carries `budgets`:
@@ -58,6 +62,8 @@ import datetime
 import re
 
 import numpy as np
+
+from . import abi
 
 NOOP, DELETE, REPLACE = 0, 1, 2
 UNLIMITED = 2**32 - 1  # KP_BUDGET_UNLIMITED
@@ -424,6 +430,87 @@ class Controller:
 
 VERDICTS = ("valid", "unscheduled", "no-replacement-needed", "multiple", "needs-replacement", "not-subset", "budget")
 _REASON = {"emptiness": EMPTY, "drift": DRIFTED, "single": UNDERUTILIZED, "multi": UNDERUTILIZED}
+
+
+# ---- Unconsolidatable events (kp_cluster_simulate_explained) -------------------------------------------------
+# Reason texts. Only the two strings R:website/content/en/preview/concepts/disruption.md:105-113 prints are pinned:
+# "pdb <ns>/<name> prevents pod evictions" and "can't replace with a lower-priced node". The rest are restated and
+# UNPINNED (disruption/consolidation.go is not among the references).
+_UNCONS_TEXT = {
+    abi.UNCONS_BUDGET: "disruption budget allows no more disruptions of its NodePool",                       # unpinned
+    abi.UNCONS_MULTIPLE_NODECLAIMS: "can't remove without creating {n_nodeclaims} candidates",                # unpinned
+    abi.UNCONS_UNSCHEDULABLE: "not all pods would schedule",                                                  # unpinned
+    abi.UNCONS_UNPRICED: "can't determine the price of the candidate's instance type",                       # unpinned
+    abi.UNCONS_SPOT_TO_SPOT_DISABLED: "SpotToSpotConsolidation is disabled, can't replace a spot node with a spot node",  # unpinned
+    abi.UNCONS_NOT_CHEAPER: "can't replace with a lower-priced node",                                         # pinned
+    abi.UNCONS_SAME_TYPE: "can't replace with a lower-priced node of another instance type",                  # unpinned
+    abi.UNCONS_SPOT_FLEXIBILITY: "SpotToSpotConsolidation requires 15 cheaper instance type options than the current "
+                                 "candidate to consolidate, got {n_same_type}",                               # unpinned
+    abi.UNCONS_MIN_VALUES: "minValues requirement is not met for the cheaper instance type options",          # unpinned
+}
+PDB_BLOCKED = abi.REASON_NAMES.index("PDB_BLOCKED")  # enum kp_candidate_reason
+_CAND_TEXT = {1: "not managed by a NodePool", 2: "node has the karpenter.sh/do-not-disrupt annotation",
+              3: "node is not initialized", 4: "node is deleting", 5: "node is nominated for a pending pod",
+              6: "pod has the karpenter.sh/do-not-disrupt annotation", 8: "consolidation is disabled (consolidateAfter Never)",
+              9: "NodePool consolidates only when empty", 10: "consolidateAfter has not elapsed", 11: "node is not empty",
+              12: "node is not drifted"}  # unpinned, all of them
+
+
+def unconsolidatable(cluster, plan, now=None, not_ready=(), extra_deleting=None):
+    """Why each managed node stays, for the single-node pass: one entry per node that carries a NodePool of the
+    cluster, in node order: {"node", "candidate_reason", "detail", "pdb", "why", "sim"}.
+      * With cluster.controls: a node that is no SingleNodeConsolidation candidate carries its kp_candidate reason and
+        detail ("pdb": (namespace, name) of the blocking PDB for KP_PDB_BLOCKED), and no simulation. Without controls
+        only the nodes being deleted are no candidates (candidate_order).
+      * Every other node carries "why", the kp_sim_why of its singleton's simulation (plan.simulate_explained, multi_node
+        False), and "sim"; under modelled budgets the candidates go through the budget walk first (reason
+        Underutilized) and one the walk skips carries the KP_UNCONS_BUDGET record without a simulation.
+    plan: the resident snapshot (ClusterPlan, or any object with the same candidates / simulate_explained)."""
+    pools = node_pools(cluster)
+    entries = {}
+    if getattr(cluster, "controls", None) is not None:
+        recs, order = candidates(cluster, plan, "single", int(_ts(now)))
+        for i in range(len(cluster.nodes)):
+            # (a kp_candidate record of the device, or the (reason, detail, ...) tuple a reference plan returns)
+            r, d = (int(recs[i]["reason"]), int(recs[i]["detail"])) if hasattr(recs[i], "dtype") else \
+                (int(recs[i][0]), int(recs[i][1]))
+            if pools[i] >= 0 and r != 0:
+                pdb = cluster.controls.pdbs[d] if r == PDB_BLOCKED else None
+                entries[i] = {"node": i, "candidate_reason": r, "detail": d, "why": None, "sim": None,
+                              "pdb": (pdb.namespace, pdb.name) if pdb is not None else None}
+        cands = [c for c in order if pools[c] >= 0]
+    else:
+        for i, n in enumerate(cluster.nodes):
+            if pools[i] >= 0 and n.deleting:
+                entries[i] = {"node": i, "candidate_reason": 4, "detail": 0, "why": None, "sim": None, "pdb": None}
+        cands = [c for c in candidate_order(cluster) if pools[c] >= 0]
+    kept = cands
+    if budgets_modelled(cluster):
+        kept = budget_walk(cluster, cands, allowed_disruptions(cluster, UNDERUTILIZED, now, not_ready, extra_deleting))
+    blocked = dict.fromkeys(abi.WHY_FIELDS, 0)
+    blocked.update(reason=abi.UNCONS_BUDGET, first_unscheduled=-1, unpriced=-1, cheapest_launch=0.0)
+    for c in set(cands) - set(kept):
+        entries[c] = {"node": c, "candidate_reason": 0, "detail": 0, "why": dict(blocked), "sim": None, "pdb": None}
+    if kept:
+        sims, whys = plan.simulate_explained([[c] for c in kept], multi_node=False)[:2]
+        for c, s, w in zip(kept, sims, whys):
+            entries[c] = {"node": c, "candidate_reason": 0, "detail": 0, "why": w, "sim": s, "pdb": None}
+    return [entries[i] for i in sorted(entries)]
+
+
+def unconsolidatable_message(entry):
+    """The Unconsolidatable event's text for an entry of unconsolidatable(), None for a node that can be consolidated
+    (reason KP_UNCONS_NONE). Pinned: "pdb <ns>/<name> prevents pod evictions" and "can't replace with a lower-priced
+    node" (disruption.md:105-113); every other text is a restatement and unpinned."""
+    r = entry["candidate_reason"]
+    if r == PDB_BLOCKED:
+        return "pdb {}/{} prevents pod evictions".format(*entry["pdb"])
+    if r:
+        return _CAND_TEXT[r]
+    w = entry["why"]
+    if w["reason"] == abi.UNCONS_NONE:
+        return None
+    return _UNCONS_TEXT[w["reason"]].format(**w)
 
 
 class Validation:
