@@ -1309,6 +1309,130 @@ typedef struct kp_candidate {
 } kp_candidate;
 int32_t kp_cluster_candidates(kp_cluster_plan* plan, const kp_candidates_in* in, kp_candidate* out /* n_nodes */,
                               uint32_t* order /* n_nodes */, uint32_t* n_candidates, kp_solve_stats* stats);
+/* Drift detection (R:pkg/cloudprovider/drift.go:43-157 CloudProvider.IsDrifted's EC2NodeClass half, R:pkg/providers/
+ * amifamily/ami.go:222-235 MapToInstanceTypes, pinned by R:pkg/cloudprovider/suite_test.go:654-1190; the NodePool hash and
+ * requirement drift of upstream core RESTATED from R:website/content/en/preview/concepts/disruption.md:131-164, parity
+ * unpinned), additive to ABI v13. One call answers IsDrifted for every node of the plan's snapshot.
+ * kp_cluster_drift is §10's simulation and is another call.
+ *
+ * Per node the first line that applies decides; reason is non-zero only when status is KP_DRIFT_OK.
+ * Status, in this order:
+ *   1 KP_DRIFT_SKIP_NOT_MANAGED        no karpenter.sh/nodepool label, or it names no NodePool of the cluster (upstream: ""
+ *                                      and a nil error); the plan's node -> pool table
+ *   2 KP_DRIFT_SKIP_NO_NODECLASS       the pool's kp_pool_drift.nodeclass is -1 (no nodeClassRef, or unresolved)
+ *     reasons 1, 2 and 3 below are judged here: before any instance lookup and before any error
+ *   3 KP_DRIFT_ERR_INSTANCE            KP_DRIFT_HAS_INSTANCE not set (no provider id, or no instance record)
+ *   4 KP_DRIFT_ERR_INSTANCE_TYPE       the node's type is not in its pool's catalogue (looked up by name when the node's
+ *                                      catalogue is another one)
+ *   5 KP_DRIFT_ERR_NO_AMIS             the nodeclass's status.amis is empty
+ *   6 KP_DRIFT_ERR_NO_SECURITY_GROUPS  its status.securityGroups is empty
+ *   7 KP_DRIFT_ERR_NO_SUBNETS          its status.subnets is empty
+ * An error ends the node with reason 0 even where an earlier dynamic check (4, 5) would have drifted: upstream returns
+ * the error.
+ * Reason, the first that applies:
+ *   1 KP_DRIFT_NODEPOOL              the pool's and the NodeClaim's karpenter.sh/nodepool-hash and -hash-version are all
+ *                                    present, the versions equal, the hashes different
+ *   2 KP_DRIFT_REQUIREMENTS          NewLabelRequirements(node labels).Compatible(pool spec.template.spec.requirements)
+ *                                    fails, undefined well-known labels not allowed (minValues and the template's labels
+ *                                    play no part); detail = the index, in the pool's list, of the first requirement
+ *                                    whose key fails
+ *   3 KP_DRIFT_NODECLASS             areStaticFieldsDrifted: the EC2NodeClass's and the NodeClaim's ec2nodeclass-hash and
+ *                                    -hash-version all present, versions equal, hashes different
+ *   4 KP_DRIFT_AMI                   the type's AMI is the first of status.amis, in order, with
+ *                                    type.Requirements.Compatible(ami requirements) (undefined keys not allowed); drifted
+ *                                    iff there is none or its id differs from the instance's image id. detail = that
+ *                                    AMI's index in status.amis, or 0xFFFFFFFF
+ *   5 KP_DRIFT_SECURITY_GROUP        the set of status.securityGroups ids differs from the set of the instance's
+ *   6 KP_DRIFT_SUBNET                the instance's subnet id is not among status.subnets
+ *   7 KP_DRIFT_CAPACITY_RESERVATION  the instance has a reservation id that is not among status.capacityReservations
+ * detail is 0 where the line gives it no meaning. The hash strings are inputs: computing them stays with the caller.
+ *
+ * counts[r] = the number of nodes with reason r (index 0: not drifted or not judged). out == NULL reads back the
+ * histogram only; out and counts both NULL is refused.
+ *
+ * Errors: KP_E_INVAL for n_pools / n_nodes that differ from the plan's snapshot, a NULL array whose count is not 0, a
+ * nodeclass index outside [-1, n_nodeclasses), an unknown requirement operator, a NULL requirement key or value, a NULL
+ * AMI / subnet / security-group / reservation id in a list, an instance (KP_DRIFT_HAS_INSTANCE) with a NULL image or
+ * subnet id; the stale-plan refusal of kp_cluster_candidates. KP_E_UNSUPPORTED (the Go path then runs) for 65,535 or
+ * more NodePools, a NodePool whose requirements name more than 65,535 distinct keys, 2^28 or more distinct label keys, and a
+ * catalogue type that some node runs carrying a NotIn / Exists / Gt / Lt requirement (the provider builds In and
+ * DoesNotExist only, R:pkg/providers/instancetype/types.go:158-292); no cap on nodes, AMIs, ids or nodeclasses beyond 2^31
+ * entries per array. Works on plans of both simulation paths, compiles the snapshot's half on its first use and keeps
+ * it resident, and leaves every other call on the plan untouched. stats: device_ms (the kernels), host_ms (the call). */
+enum kp_drift_status {
+  KP_DRIFT_OK = 0,
+  KP_DRIFT_SKIP_NOT_MANAGED = 1,
+  KP_DRIFT_SKIP_NO_NODECLASS = 2,
+  KP_DRIFT_ERR_INSTANCE = 3,
+  KP_DRIFT_ERR_INSTANCE_TYPE = 4,
+  KP_DRIFT_ERR_NO_AMIS = 5,
+  KP_DRIFT_ERR_NO_SECURITY_GROUPS = 6,
+  KP_DRIFT_ERR_NO_SUBNETS = 7
+};
+enum kp_drift_reason {
+  KP_DRIFT_NONE = 0,
+  KP_DRIFT_NODEPOOL = 1,
+  KP_DRIFT_REQUIREMENTS = 2,
+  KP_DRIFT_NODECLASS = 3,
+  KP_DRIFT_AMI = 4,
+  KP_DRIFT_SECURITY_GROUP = 5,
+  KP_DRIFT_SUBNET = 6,
+  KP_DRIFT_CAPACITY_RESERVATION = 7,
+  KP_DRIFT_REASON_COUNT = 8
+};
+typedef struct kp_ami {               /* one entry of EC2NodeClass status.amis */
+  const char* id;
+  kp_requirements requirements;
+} kp_ami;
+typedef struct kp_nodeclass_status {  /* EC2NodeClass annotations + status, as drift reads them */
+  const char* hash;                   /* karpenter.k8s.aws/ec2nodeclass-hash; NULL: absent */
+  const char* hash_version;           /* ...-hash-version; NULL: absent */
+  const kp_ami* amis;                 /* in status order */
+  const char* const* subnets;         /* status.subnets[].id */
+  const char* const* security_groups; /* status.securityGroups[].id */
+  const char* const* capacity_reservations; /* status.capacityReservations[].id */
+  uint32_t n_amis;
+  uint32_t n_subnets;
+  uint32_t n_security_groups;
+  uint32_t n_capacity_reservations;
+} kp_nodeclass_status;
+typedef struct kp_pool_drift {        /* indexed like kp_cluster.nodepools */
+  int32_t nodeclass;                  /* index into kp_drift_in.nodeclasses, or -1 */
+  int32_t reserved_;
+  const char* hash;                   /* the NodePool's karpenter.sh/nodepool-hash; NULL: absent */
+  const char* hash_version;
+} kp_pool_drift;
+#define KP_DRIFT_HAS_INSTANCE 1u
+typedef struct kp_node_drift_in {     /* indexed like kp_cluster.nodes: the NodeClaim's annotations and its instance */
+  uint32_t flags;                     /* KP_DRIFT_HAS_INSTANCE: a provider id that resolves to an instance record */
+  uint32_t n_security_groups;
+  const char* nodepool_hash;          /* the NodeClaim's four annotations; NULL: absent */
+  const char* nodepool_hash_version;
+  const char* nodeclass_hash;
+  const char* nodeclass_hash_version;
+  const char* image_id;               /* the instance's; read when KP_DRIFT_HAS_INSTANCE */
+  const char* subnet_id;
+  const char* const* security_groups;
+  const char* capacity_reservation_id; /* NULL: none */
+} kp_node_drift_in;
+typedef struct kp_drift_in {
+  const kp_nodeclass_status* nodeclasses;
+  const kp_pool_drift* pools;
+  const kp_node_drift_in* nodes;
+  uint32_t n_nodeclasses;
+  uint32_t n_pools;                   /* == kp_cluster.n_nodepools */
+  uint32_t n_nodes;                   /* == kp_cluster.n_nodes */
+  uint32_t reserved_;
+} kp_drift_in;
+typedef struct kp_node_drift {
+  int32_t reason;                     /* enum kp_drift_reason */
+  int32_t status;                     /* enum kp_drift_status */
+  uint32_t detail;
+  uint32_t reserved_;
+} kp_node_drift;
+int32_t kp_cluster_detect_drift(kp_cluster_plan* plan, const kp_drift_in* in, kp_node_drift* out /* n_nodes */,
+                                uint64_t* counts /* KP_DRIFT_REASON_COUNT words, may be NULL */,
+                                kp_solve_stats* stats);
 /* The reduction kp_consolidate_argmin applies to the gathered per-rank records (host-only; exposed for callers that
  * reduce over another transport, and for tests): counts are summed, the best record wins. */
 int32_t kp_choice_reduce(const kp_choice* per_rank, uint32_t n, kp_choice* out);

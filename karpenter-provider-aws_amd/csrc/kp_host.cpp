@@ -32,6 +32,7 @@
 
 #include "kp/kp_abi.h"
 #include "kp_cand.h"
+#include "kp_driftdet.h"
 #include "kp_device.h"
 #include "kp_model.h"
 
@@ -5069,6 +5070,7 @@ struct CandState {
   size_t call_bytes = 0;
 };
 
+struct DriftState;
 struct GeneralBatch;
 struct kp_cluster_plan {
   CtxRef ctx;
@@ -5111,6 +5113,7 @@ struct kp_cluster_plan {
   const uint16_t* d_node_pool = nullptr;  // its resident copy (batched path)
   uint32_t n_pools = 0;
   std::unique_ptr<CandState> cand;        // kp_cluster_candidates, built on its first call
+  std::shared_ptr<DriftState> drift;      // kp_cluster_detect_drift, built on its first call
 };
 
 // kp_*_budgeted: the caller's allowed[] and the count of subsets it blocked
@@ -8383,6 +8386,464 @@ int32_t kp_cluster_candidates(kp_cluster_plan* plan, const kp_candidates_in* in,
   HIPCHK(hipStreamSynchronize(st));
   if (n > N) return fail(KP_E_DEVICE, "the device counted %u candidates of %u nodes", n, N);
   *n_candidates = n;
+  if (stats) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    stats->device_ms = ms;
+    stats->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return KP_OK;
+}
+
+}  // extern "C"
+
+// ---- Drift detection (kp_cluster_detect_drift) ---------------------------------------------------------------------
+// The host does strings only. Once per plan (DriftBuild): the node -> pool table, each node's type inside its pool's
+// catalogue, the nodes' label values as ids of per-key dictionaries, each pool's merged requirement per key evaluated
+// against that dictionary into a bitset, and the requirement rows of the types the nodes run. Per call: the hashes and
+// ids interned, the id lists sorted, the AMI requirements compiled into tokens. The ladder is the device's
+// (kp_driftdet.hip).
+static_assert(sizeof(DrOut) == sizeof(kp_node_drift) && sizeof(kp_node_drift) == 16, "DrOut mirrors kp_node_drift");
+
+namespace {
+// scheduling.Requirement on strings: a value set or its complement, with the Gt / Lt bounds a complement carries
+struct SReq {
+  std::set<string> values;
+  bool complement = false, has_gt = false, has_lt = false;
+  int64_t gt = 0, lt = 0;
+  // Operator() is NotIn or DoesNotExist
+  bool NegOp() const { return complement ? !values.empty() : values.empty(); }
+  bool Within(const string& v) const {
+    if (!has_gt && !has_lt) return true;
+    int64_t x;
+    if (!Atoi(v, &x)) return false;
+    return !(has_gt && gt >= x) && !(has_lt && lt <= x);
+  }
+  // Intersection(In {v}, *this) is not empty
+  bool Admits(const string& v) const { return (values.count(v) != 0) != complement && Within(v); }
+};
+SReq SReqOf(const kp_requirement& q) {  // NewRequirement
+  SReq r;
+  auto val = [&](uint32_t j) { return string(q.values[j] ? q.values[j] : ""); };
+  if (q.op == KP_OP_IN) {
+    for (uint32_t j = 0; j < q.n_values; j++) r.values.insert(val(j));
+    return r;
+  }
+  r.complement = q.op != KP_OP_DOES_NOT_EXIST;
+  if (q.op == KP_OP_NOT_IN)
+    for (uint32_t j = 0; j < q.n_values; j++) r.values.insert(val(j));
+  if (q.op == KP_OP_GT || q.op == KP_OP_LT) {
+    int64_t x = 0;
+    if (q.n_values) (void)Atoi(val(0), &x);  // validated upstream; an Atoi error leaves 0
+    if (q.op == KP_OP_GT) r.has_gt = true, r.gt = x;
+    else r.has_lt = true, r.lt = x;
+  }
+  return r;
+}
+SReq SReqMerge(const SReq& a, const SReq& b) {  // Requirement.Intersection, what Requirements.Add keeps
+  SReq o;
+  const bool hg = a.has_gt || b.has_gt, hl = a.has_lt || b.has_lt;
+  const int64_t gt = a.has_gt && b.has_gt ? std::max(a.gt, b.gt) : a.has_gt ? a.gt : b.gt;
+  const int64_t lt = a.has_lt && b.has_lt ? std::min(a.lt, b.lt) : a.has_lt ? a.lt : b.lt;
+  if (hg && hl && gt >= lt) return o;  // DoesNotExist
+  SReq bound;
+  bound.has_gt = hg, bound.gt = gt, bound.has_lt = hl, bound.lt = lt;
+  if (a.complement && b.complement) {
+    o.values = a.values;
+    o.values.insert(b.values.begin(), b.values.end());
+  } else {
+    const SReq& pos = a.complement ? b : a;
+    const SReq& other = a.complement ? a : b;
+    for (auto& v : pos.values)
+      if ((other.values.count(v) != 0) != other.complement) o.values.insert(v);
+  }
+  for (auto it = o.values.begin(); it != o.values.end();)
+    it = bound.Within(*it) ? std::next(it) : o.values.erase(it);
+  o.complement = a.complement && b.complement;
+  if (o.complement) o.has_gt = hg, o.gt = gt, o.has_lt = hl, o.lt = lt;
+  return o;
+}
+int32_t CheckReqs(const kp_requirements& r, const char* who, uint32_t i, uint32_t j) {
+  if (r.n && !r.items) return fail(KP_E_INVAL, "%s %u.%u: null requirements", who, i, j);
+  for (uint32_t k = 0; k < r.n; k++) {
+    const kp_requirement& q = r.items[k];
+    if (!q.key) return fail(KP_E_INVAL, "%s %u.%u: null requirement key", who, i, j);
+    if (q.op < KP_OP_IN || q.op > KP_OP_LT) return fail(KP_E_INVAL, "%s %u.%u: operator %d", who, i, j, q.op);
+    if (q.n_values && !q.values) return fail(KP_E_INVAL, "%s %u.%u: null values", who, i, j);
+    for (uint32_t v = 0; v < q.n_values; v++)
+      if (!q.values[v]) return fail(KP_E_INVAL, "%s %u.%u: null value", who, i, j);
+  }
+  return KP_OK;
+}
+// requirements merged per normalized key, in key order
+int32_t MergeReqs(const kp_requirements& r, std::map<string, SReq>& out) {
+  for (uint32_t k = 0; k < r.n; k++) {
+    const SReq q = SReqOf(r.items[k]);
+    auto ins = out.emplace(Normalize(r.items[k].key), q);
+    if (!ins.second) ins.first->second = SReqMerge(q, ins.first->second);
+  }
+  return KP_OK;
+}
+}  // namespace
+
+struct DriftState {
+  DevBuf buf;
+  DriftDetArgs a{};                                          // the resident half of the kernel arguments
+  vector<vector<uint32_t>> pool_types;                    // per pool the distinct used types its nodes run
+  std::unordered_map<string, uint32_t> tkey_id;           // keys of the used types' requirements
+  vector<std::unordered_map<string, uint32_t>> tval_id;   // per such key the values some used type holds
+  vector<vector<string>> tvals;                           // the same by id
+  DevBuf call;
+  size_t call_bytes = 0;
+};
+
+static int32_t DriftBuild(kp_cluster_plan* plan) {
+  kp_ctx* ctx = plan->ctx;
+  const kp_cluster& cl = plan->cluster()->cl;
+  const uint32_t N = cl.n_nodes, P = cl.n_nodepools;
+  if (P >= 0xFFFF) return fail(KP_E_UNSUPPORTED, "drift detection over %u NodePools (max 65534)", P);
+  auto ds = std::make_shared<DriftState>();
+  // the pools' requirements: the union of their keys, each pool's merged requirement per key
+  std::unordered_map<string, uint32_t> key_id;
+  struct PoolKey {
+    uint32_t key, first;
+    SReq req;
+  };
+  vector<vector<PoolKey>> pkeys(P);
+  for (uint32_t p = 0; p < P; p++) {
+    const kp_requirements& r = cl.nodepools[p].requirements;
+    if (int32_t rc = CheckReqs(r, "NodePool", p, 0)) return rc;
+    std::unordered_map<uint32_t, size_t> at;
+    for (uint32_t j = 0; j < r.n; j++) {
+      const uint32_t k = key_id.emplace(Normalize(r.items[j].key), (uint32_t)key_id.size()).first->second;
+      const SReq q = SReqOf(r.items[j]);
+      auto f = at.find(k);
+      if (f == at.end()) {
+        at.emplace(k, pkeys[p].size());
+        pkeys[p].push_back({k, j, q});
+      } else {
+        pkeys[p][f->second].req = SReqMerge(q, pkeys[p][f->second].req);
+      }
+    }
+    if (pkeys[p].size() > 0xFFFF) return fail(KP_E_UNSUPPORTED, "NodePool %u names %zu distinct keys (max 65535)", p, pkeys[p].size());
+  }
+  const uint32_t K = (uint32_t)key_id.size();
+  if (K >= (1u << 28)) return fail(KP_E_UNSUPPORTED, "%u distinct requirement keys (max 2^28 - 1)", K);
+  // the nodes' values under those keys, key-major; two labels that normalize to one key with different values leave
+  // DoesNotExist, which Compatible treats as it treats a missing label
+  vector<std::unordered_map<string, uint32_t>> val_id(K);
+  vector<vector<string>> vals(K);
+  vector<uint32_t> node_val((size_t)K * N, DR_NONE), node_pool(std::max<uint32_t>(N, 1), DR_NONE), node_type(std::max<uint32_t>(N, 1), DR_NONE);
+  vector<uint8_t> clash((size_t)K, 0);
+  for (uint32_t i = 0; i < N; i++) {
+    const kp_existing_node& n = cl.nodes[i].node;
+    if (n.n_labels && !n.labels) return fail(KP_E_INVAL, "node %u: null labels", i);
+    std::fill(clash.begin(), clash.end(), 0);
+    for (uint32_t j = 0; j < n.n_labels && K; j++) {
+      if (!n.labels[j].key) return fail(KP_E_INVAL, "node %u: null label key", i);
+      auto f = key_id.find(Normalize(n.labels[j].key));
+      if (f == key_id.end()) continue;
+      const uint32_t k = f->second;
+      const string v = n.labels[j].value ? n.labels[j].value : "";
+      auto ins = val_id[k].emplace(v, (uint32_t)val_id[k].size());
+      if (ins.second) vals[k].push_back(v);
+      uint32_t& slot = node_val[(size_t)k * N + i];
+      if (clash[k] || (slot != DR_NONE && slot != ins.first->second)) clash[k] = 1, slot = DR_NONE;
+      else slot = ins.first->second;
+    }
+    if (plan->node_pool[i] != 0xFFFF) node_pool[i] = plan->node_pool[i];
+  }
+  // each pool's merged requirements against the dictionaries
+  vector<uint32_t> pool_key_off(P + 1, 0), pk_key, pk_first, pk_bits;
+  vector<uint64_t> pass_bits;
+  for (uint32_t p = 0; p < P; p++) {
+    for (const PoolKey& e : pkeys[p]) {
+      if (e.first >= DR_ABSENT_PASSES || pass_bits.size() >= 0xFFFFFFFFull) return fail(KP_E_UNSUPPORTED, "NodePool %u: too many requirements", p);
+      pk_key.push_back(e.key);
+      pk_first.push_back(e.first | (e.req.NegOp() ? DR_ABSENT_PASSES : 0));
+      pk_bits.push_back((uint32_t)pass_bits.size());
+      const size_t base = pass_bits.size();
+      pass_bits.resize(base + std::max<size_t>(1, (vals[e.key].size() + 63) / 64), 0);
+      for (size_t v = 0; v < vals[e.key].size(); v++)
+        if (e.req.Admits(vals[e.key][v])) pass_bits[base + (v >> 6)] |= 1ull << (v & 63);
+    }
+    pool_key_off[p + 1] = (uint32_t)pk_key.size();
+  }
+  // each node's type inside its pool's catalogue, and the distinct (catalogue, type) pairs: the used types
+  std::map<std::pair<uint32_t, uint32_t>, uint32_t> used;
+  vector<std::pair<uint32_t, uint32_t>> used_list;
+  vector<std::unordered_map<string, uint32_t>> by_name(cl.n_catalogs);
+  vector<std::set<uint32_t>> pool_types(P);
+  for (uint32_t i = 0; i < N; i++) {
+    if (node_pool[i] == DR_NONE) continue;
+    const kp_cluster_node& n = cl.nodes[i];
+    const uint32_t pc = cl.nodepools[node_pool[i]].catalog;
+    if (pc >= cl.n_catalogs) return fail(KP_E_INVAL, "NodePool %u names catalogue %u of %u", node_pool[i], pc, cl.n_catalogs);
+    const vector<HostType>& ptypes = cl.catalogs[pc]->types;
+    uint32_t t = DR_NONE;
+    if (n.catalog == pc) {
+      if (n.instance_type < ptypes.size()) t = n.instance_type;
+    } else if (n.catalog < cl.n_catalogs && n.instance_type < cl.catalogs[n.catalog]->types.size()) {
+      auto& names = by_name[pc];
+      if (names.empty())
+        for (uint32_t x = 0; x < ptypes.size(); x++) names.emplace(ptypes[x].name, x);
+      auto f = names.find(cl.catalogs[n.catalog]->types[n.instance_type].name);
+      if (f != names.end()) t = f->second;
+    }
+    if (t == DR_NONE) continue;
+    auto ins = used.emplace(std::make_pair(pc, t), (uint32_t)used.size());
+    if (ins.second) used_list.push_back({pc, t});
+    node_type[i] = ins.first->second;
+    pool_types[node_pool[i]].insert(ins.first->second);
+  }
+  const uint32_t U = (uint32_t)used_list.size();
+  ds->pool_types.resize(P);
+  for (uint32_t p = 0; p < P; p++) ds->pool_types[p].assign(pool_types[p].begin(), pool_types[p].end());
+  // the used types' requirement rows: keys, per key the values some used type holds, per (type, key) the held set
+  vector<std::map<string, SReq>> treqs(U);
+  for (uint32_t u = 0; u < U; u++) {
+    const HostType& ht = cl.catalogs[used_list[u].first]->types[used_list[u].second];
+    for (const RawReq& r : ht.reqs) {
+      const char* none = nullptr;
+      vector<const char*> vp;
+      for (auto& v : r.values) vp.push_back(v.c_str());
+      kp_requirement q{r.key.c_str(), r.op, -1, vp.empty() ? &none : vp.data(), (uint32_t)vp.size(), 0};
+      const SReq s = SReqOf(q);
+      auto ins = treqs[u].emplace(Normalize(r.key), s);
+      if (!ins.second) ins.first->second = SReqMerge(s, ins.first->second);
+    }
+    for (auto& kv : treqs[u]) {
+      if (kv.second.complement)
+        return fail(KP_E_UNSUPPORTED, "instance type %s: a NotIn / Exists / Gt / Lt requirement on %s", ht.name.c_str(), kv.first.c_str());
+      const uint32_t k = ds->tkey_id.emplace(kv.first, (uint32_t)ds->tkey_id.size()).first->second;
+      if (k >= ds->tval_id.size()) ds->tval_id.resize(k + 1), ds->tvals.resize(k + 1);
+      for (auto& v : kv.second.values)
+        if (ds->tval_id[k].emplace(v, (uint32_t)ds->tval_id[k].size()).second) ds->tvals[k].push_back(v);
+    }
+  }
+  const uint32_t TK = (uint32_t)ds->tkey_id.size();
+  if (TK > DR_TOK_KEY) return fail(KP_E_UNSUPPORTED, "%u distinct keys over the instance types (max 2^24 - 1)", TK);
+  vector<uint32_t> tkey_off(std::max<uint32_t>(TK, 1), 0);
+  size_t TW = 0;
+  for (uint32_t k = 0; k < TK; k++) {
+    tkey_off[k] = (uint32_t)TW;
+    TW += std::max<size_t>(1, (ds->tvals[k].size() + 63) / 64);
+  }
+  if (TW > 0x7FFFFFFFull || (uint64_t)U * std::max<uint32_t>(TK, 1) > 0x7FFFFFFFull)
+    return fail(KP_E_UNSUPPORTED, "the instance types' requirement table is too large");
+  vector<uint32_t> type_cnt((size_t)U * TK, DR_NONE);
+  vector<uint64_t> type_bits((size_t)U * TW, 0);
+  for (uint32_t u = 0; u < U; u++)
+    for (auto& kv : treqs[u]) {
+      const uint32_t k = ds->tkey_id[kv.first];
+      type_cnt[(size_t)u * TK + k] = (uint32_t)kv.second.values.size();
+      for (auto& v : kv.second.values) {
+        const uint32_t id = ds->tval_id[k][v];
+        type_bits[(size_t)u * TW + tkey_off[k] + (id >> 6)] |= 1ull << (id & 63);
+      }
+    }
+  Blob blob;
+  const size_t o_pool = blob.put(node_pool), o_type = blob.put(node_type), o_val = blob.put(node_val),
+               o_koff = blob.put(pool_key_off), o_pkk = blob.put(pk_key), o_pkf = blob.put(pk_first),
+               o_pkb = blob.put(pk_bits), o_pass = blob.put(pass_bits), o_tcnt = blob.put(type_cnt),
+               o_tbits = blob.put(type_bits), o_toff = blob.put(tkey_off);
+  HIPCHK(ds->buf.alloc(blob.total()));
+  uint8_t* base = (uint8_t*)ds->buf.p;
+  HIPCHK(hipMemcpyAsync(base, blob.host.data(), blob.host.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  DriftDetArgs& a = ds->a;
+  a.node_pool = (const uint32_t*)(base + o_pool), a.node_type = (const uint32_t*)(base + o_type);
+  a.node_val = (const uint32_t*)(base + o_val), a.pool_key_off = (const uint32_t*)(base + o_koff);
+  a.pk_key = (const uint32_t*)(base + o_pkk), a.pk_first = (const uint32_t*)(base + o_pkf);
+  a.pk_bits = (const uint32_t*)(base + o_pkb), a.pass_bits = (const uint64_t*)(base + o_pass);
+  a.type_cnt = (const uint32_t*)(base + o_tcnt), a.type_bits = (const uint64_t*)(base + o_tbits);
+  a.tkey_off = (const uint32_t*)(base + o_toff);
+  a.n_types = (int)U, a.n_tkeys = (int)TK, a.type_words = (int)TW, a.n_nodes = (int)N;
+  plan->drift = std::move(ds);
+  return KP_OK;
+}
+
+// One AMI's requirements as tokens over the used types' dictionary (kp_driftdet.h)
+static void DriftCompileAmi(const DriftState& ds, const std::map<string, SReq>& reqs, vector<uint32_t>& tok) {
+  const size_t start = tok.size();
+  for (auto& kv : reqs) {
+    const SReq& r = kv.second;
+    auto f = ds.tkey_id.find(kv.first);
+    if (f == ds.tkey_id.end()) {  // no type defines the key
+      if (r.NegOp()) continue;
+      tok.resize(start);
+      tok.push_back(DR_TOK_NEVER);
+      return;
+    }
+    const uint32_t k = f->second;
+    const size_t hdr = tok.size();
+    tok.push_back(k | (r.complement ? DR_TOK_NOT : DR_TOK_ANY) | (r.NegOp() ? DR_TOK_NEGOP : 0));
+    tok.push_back(0);
+    if (!r.complement) {  // a value no type carries meets nothing
+      for (auto& v : r.values) {
+        auto id = ds.tval_id[k].find(v);
+        if (id != ds.tval_id[k].end()) tok.push_back(id->second);
+      }
+    } else {              // ... and is refused in vain
+      for (uint32_t id = 0; id < ds.tvals[k].size(); id++)
+        if (r.values.count(ds.tvals[k][id]) || !r.Within(ds.tvals[k][id])) tok.push_back(id);
+    }
+    tok[hdr + 1] = (uint32_t)(tok.size() - hdr - 2);
+  }
+}
+
+extern "C" {
+
+int32_t kp_cluster_detect_drift(kp_cluster_plan* plan, const kp_drift_in* in, kp_node_drift* out, uint64_t* counts,
+                                kp_solve_stats* stats) {
+  if (!plan || !in) return fail(KP_E_INVAL, "null argument");
+  if (!out && !counts) return fail(KP_E_INVAL, "null out and counts");
+  kp_ctx* ctx = plan->ctx;
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  HIPCHK(hipSetDevice(ctx->device));
+  if (stats) memset(stats, 0, sizeof *stats);
+  const auto t0 = std::chrono::steady_clock::now();
+  const OwnedCluster* oc = plan->cluster();
+  if (!oc) return fail(KP_E_INVAL, "the plan holds no cluster");
+  if (plan->general) {
+    if (int32_t rc = CatalogsAlive(oc->alive)) return rc;
+  } else {  // a plan of the batched simulation kernel: kp_cluster_simulate's stale-plan refusal
+    if (int32_t rc = CatalogsAlive(plan->cp->B->alive)) return rc;
+    if (SeqnumsOf(plan->cp->B->catalogs) != plan->cp->B->seqnums)
+      return fail(KP_E_INVAL, "stale plan: a catalogue's seqnum changed since it was prepared (kp_cluster_refresh)");
+  }
+  const kp_cluster& cl = oc->cl;
+  if (in->n_pools != cl.n_nodepools || in->n_nodes != cl.n_nodes)
+    return fail(KP_E_INVAL, "drift inputs for %u NodePools, %u nodes; the plan's snapshot has %u, %u", in->n_pools, in->n_nodes,
+                cl.n_nodepools, cl.n_nodes);
+  if ((in->n_pools && !in->pools) || (in->n_nodes && !in->nodes) || (in->n_nodeclasses && !in->nodeclasses))
+    return fail(KP_E_INVAL, "null nodeclasses, pools or nodes");
+  const uint32_t N = in->n_nodes, P = in->n_pools, C = in->n_nodeclasses;
+  if (C > 0x7FFFFFFFu) return fail(KP_E_UNSUPPORTED, "%u nodeclasses", C);
+  for (uint32_t p = 0; p < P; p++)
+    if (in->pools[p].nodeclass < -1 || in->pools[p].nodeclass >= (int32_t)C)
+      return fail(KP_E_INVAL, "NodePool %u: nodeclass %d of %u", p, in->pools[p].nodeclass, C);
+  for (uint32_t c = 0; c < C; c++) {
+    const kp_nodeclass_status& s = in->nodeclasses[c];
+    if ((s.n_amis && !s.amis) || (s.n_subnets && !s.subnets) || (s.n_security_groups && !s.security_groups) ||
+        (s.n_capacity_reservations && !s.capacity_reservations))
+      return fail(KP_E_INVAL, "nodeclass %u: null array", c);
+    for (uint32_t j = 0; j < s.n_amis; j++) {
+      if (!s.amis[j].id) return fail(KP_E_INVAL, "nodeclass %u: AMI %u has a null id", c, j);
+      if (int32_t rc = CheckReqs(s.amis[j].requirements, "AMI", c, j)) return rc;
+    }
+    for (uint32_t j = 0; j < s.n_subnets; j++)
+      if (!s.subnets[j]) return fail(KP_E_INVAL, "nodeclass %u: null subnet id", c);
+    for (uint32_t j = 0; j < s.n_security_groups; j++)
+      if (!s.security_groups[j]) return fail(KP_E_INVAL, "nodeclass %u: null security-group id", c);
+    for (uint32_t j = 0; j < s.n_capacity_reservations; j++)
+      if (!s.capacity_reservations[j]) return fail(KP_E_INVAL, "nodeclass %u: null capacity-reservation id", c);
+  }
+  for (uint32_t i = 0; i < N; i++) {
+    const kp_node_drift_in& n = in->nodes[i];
+    if (!(n.flags & KP_DRIFT_HAS_INSTANCE)) continue;
+    if (!n.image_id || !n.subnet_id) return fail(KP_E_INVAL, "node %u: an instance with a null image or subnet id", i);
+    if (n.n_security_groups && !n.security_groups) return fail(KP_E_INVAL, "node %u: null security groups", i);
+    for (uint32_t j = 0; j < n.n_security_groups; j++)
+      if (!n.security_groups[j]) return fail(KP_E_INVAL, "node %u: null security-group id", i);
+  }
+  if (!plan->drift)
+    if (int32_t rc = DriftBuild(plan)) return rc;
+  DriftState& ds = *plan->drift;
+  const uint32_t U = (uint32_t)ds.a.n_types;
+  if ((uint64_t)C * std::max<uint32_t>(U, 1) > 0x7FFFFFFFull) return fail(KP_E_UNSUPPORTED, "%u nodeclasses x %u instance types", C, U);
+  // strings to integers
+  std::unordered_map<string, uint32_t> ids;
+  auto intern = [&](const char* s) { return s ? ids.emplace(s, (uint32_t)ids.size()).first->second : DR_NONE; };
+  auto sorted_ids = [&](const char* const* s, uint32_t n, vector<uint32_t>& into) {
+    const size_t lo = into.size();
+    for (uint32_t j = 0; j < n; j++) into.push_back(intern(s[j]));
+    std::sort(into.begin() + lo, into.end());
+    into.erase(std::unique(into.begin() + lo, into.end()), into.end());
+    return (uint32_t)(into.size() - lo);
+  };
+  vector<DrClass> classes(std::max<uint32_t>(C, 1));
+  vector<uint32_t> class_ids, ami_id, ami_tok_off(1, 0), ami_tok;
+  for (uint32_t c = 0; c < C; c++) {
+    const kp_nodeclass_status& s = in->nodeclasses[c];
+    DrClass& d = classes[c];
+    d.hash = intern(s.hash), d.version = intern(s.hash_version);
+    d.ami_off = (uint32_t)ami_id.size(), d.n_amis = s.n_amis;
+    for (uint32_t j = 0; j < s.n_amis; j++) {
+      ami_id.push_back(intern(s.amis[j].id));
+      std::map<string, SReq> merged;
+      MergeReqs(s.amis[j].requirements, merged);
+      DriftCompileAmi(ds, merged, ami_tok);
+      if (ami_tok.size() >= (1ull << 31) || ami_id.size() >= (1ull << 31)) return fail(KP_E_UNSUPPORTED, "2^31 or more AMIs or AMI terms");
+      ami_tok_off.push_back((uint32_t)ami_tok.size());
+    }
+    d.sg_off = (uint32_t)class_ids.size(), d.n_sg = sorted_ids(s.security_groups, s.n_security_groups, class_ids);
+    d.subnet_off = (uint32_t)class_ids.size(), d.n_subnets = sorted_ids(s.subnets, s.n_subnets, class_ids);
+    d.res_off = (uint32_t)class_ids.size();
+    d.n_res = sorted_ids(s.capacity_reservations, s.n_capacity_reservations, class_ids);
+    if (class_ids.size() >= (1ull << 31)) return fail(KP_E_UNSUPPORTED, "2^31 or more nodeclass ids");
+  }
+  vector<DrPool> pools(std::max<uint32_t>(P, 1));
+  vector<uint8_t> want((size_t)C * U, 0);
+  vector<uint32_t> pairs;
+  for (uint32_t p = 0; p < P; p++) {
+    pools[p] = DrPool{in->pools[p].nodeclass, intern(in->pools[p].hash), intern(in->pools[p].hash_version), 0};
+    if (in->pools[p].nodeclass < 0) continue;
+    for (uint32_t u : ds.pool_types[p]) {
+      const size_t pair = (size_t)in->pools[p].nodeclass * U + u;
+      if (!want[pair]) want[pair] = 1, pairs.push_back((uint32_t)pair);
+    }
+  }
+  vector<DrNode> nodes(std::max<uint32_t>(N, 1));
+  vector<uint32_t> node_sg_off(N + 1, 0), node_sg;
+  for (uint32_t i = 0; i < N; i++) {
+    const kp_node_drift_in& n = in->nodes[i];
+    const bool inst = (n.flags & KP_DRIFT_HAS_INSTANCE) != 0;
+    nodes[i] = DrNode{inst ? KP_DRIFT_HAS_INSTANCE : 0u,
+                      intern(n.nodepool_hash),
+                      intern(n.nodepool_hash_version),
+                      intern(n.nodeclass_hash),
+                      intern(n.nodeclass_hash_version),
+                      inst ? intern(n.image_id) : DR_NONE,
+                      inst ? intern(n.subnet_id) : DR_NONE,
+                      inst ? intern(n.capacity_reservation_id) : DR_NONE};
+    if (inst) sorted_ids(n.security_groups, n.n_security_groups, node_sg);
+    if (node_sg.size() >= (1ull << 31)) return fail(KP_E_UNSUPPORTED, "2^31 or more security-group references");
+    node_sg_off[i + 1] = (uint32_t)node_sg.size();
+  }
+  DriftDetArgs a = ds.a;
+  Blob blob;
+  const size_t o_pools = blob.put(pools), o_nodes = blob.put(nodes), o_classes = blob.put(classes),
+               o_sgoff = blob.put(node_sg_off), o_sg = blob.put(node_sg), o_cids = blob.put(class_ids),
+               o_amiid = blob.put(ami_id), o_toff = blob.put(ami_tok_off), o_tok = blob.put(ami_tok),
+               o_pairs = blob.put(pairs);
+  const size_t o_amiof = blob.reserve_dev(sizeof(uint32_t) * std::max<size_t>((size_t)C * U, 1)),
+               o_out = blob.reserve_dev(sizeof(DrOut) * std::max<uint32_t>(N, 1)),
+               o_part = blob.reserve_dev(sizeof(uint64_t) * DR_REASONS * DR_COUNT_MAX_BLOCKS),
+               o_counts = blob.reserve_dev(sizeof(uint64_t) * DR_REASONS);
+  if (blob.total() > ds.call_bytes) {
+    HIPCHK(ds.call.alloc(blob.total()));
+    ds.call_bytes = blob.total();
+  }
+  uint8_t* base = (uint8_t*)ds.call.p;
+  a.pools = (const DrPool*)(base + o_pools), a.nodes = (const DrNode*)(base + o_nodes);
+  a.classes = (const DrClass*)(base + o_classes), a.node_sg_off = (const uint32_t*)(base + o_sgoff);
+  a.node_sg = (const uint32_t*)(base + o_sg), a.class_ids = (const uint32_t*)(base + o_cids);
+  a.ami_id = (const uint32_t*)(base + o_amiid), a.ami_tok_off = (const uint32_t*)(base + o_toff);
+  a.ami_tok = (const uint32_t*)(base + o_tok), a.pairs = (const uint32_t*)(base + o_pairs);
+  a.n_pairs = (int)pairs.size();
+  a.ami_of = (uint32_t*)(base + o_amiof), a.out = (DrOut*)(base + o_out);
+  a.part = (uint64_t*)(base + o_part), a.counts = (uint64_t*)(base + o_counts);
+  hipStream_t st = ctx->stream;
+  HIPCHK(hipMemcpyAsync(base, blob.host.data(), blob.host.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(hipEventRecord(ctx->ev0, st));
+  HIPCHK(launch_detect_drift(a, st));
+  HIPCHK(hipEventRecord(ctx->ev1, st));
+  uint64_t hist[DR_REASONS] = {};
+  if (out && N) HIPCHK(hipMemcpyAsync(out, a.out, sizeof(DrOut) * N, hipMemcpyDeviceToHost, st));
+  if (counts) HIPCHK(hipMemcpyAsync(hist, a.counts, sizeof hist, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (counts) memcpy(counts, hist, sizeof hist);
   if (stats) {
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));

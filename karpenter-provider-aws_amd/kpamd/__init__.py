@@ -136,6 +136,8 @@ def load_lib(path=None):
                                             P(C.c_uint64), P(abi.SolveStats)]),
         "kp_cluster_candidates": (C.c_int32, [C.c_void_p, P(abi.CandidatesIn), C.c_void_p, P(C.c_uint32), P(C.c_uint32),
                                               P(abi.SolveStats)]),
+        "kp_cluster_detect_drift": (C.c_int32, [C.c_void_p, P(abi.DriftIn), C.c_void_p, P(C.c_uint64),
+                                                P(abi.SolveStats)]),
         "kp_cluster_simulate_explained": (C.c_int32, [C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32), C.c_uint32,
                                                       C.c_int32, P(C.c_uint32), C.c_uint32, P(abi.SimResult),
                                                       P(abi.SimWhy), P(C.c_uint64), P(C.c_uint64), P(abi.SolveStats)]),
@@ -874,6 +876,23 @@ class ClusterPlan:
                                                                 order.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                                 C.byref(count), C.byref(st)))
         return out[:n], [int(x) for x in order[:count.value]], stats_dict(st)
+
+    def detect_drift(self, inputs=None, records=True):
+        """kp_cluster_detect_drift on inputs (default: the cluster's DriftInputs): IsDrifted for every node of the
+        snapshot in one call. Returns (records, counts, stats): records the numpy array of abi.node_drift_dtype(), one
+        per node (reason: abi.DRIFT_*, non-zero only when status is DRIFT_OK); counts the abi.DRIFT_REASON_COUNT-entry
+        histogram of the reasons. records=False passes out = NULL: records is None and only the histogram is read back."""
+        inputs = self.cluster.drift_inputs if inputs is None else inputs
+        if inputs is None:
+            raise ValueError("the cluster carries no DriftInputs")
+        arena = Arena()
+        di = abi.build_drift_in(arena, inputs)
+        n = len(inputs.nodes)
+        out = np.zeros(max(n, 1), dtype=abi.node_drift_dtype()) if records else None
+        counts, st = (C.c_uint64 * abi.DRIFT_REASON_COUNT)(), abi.SolveStats()
+        _check(self.ctx.lib, self.ctx.lib.kp_cluster_detect_drift(self.h, C.byref(di), out.ctypes.data if records else None,
+                                                                  counts, C.byref(st)))
+        return (out[:n] if records else None), [int(c) for c in counts], stats_dict(st)
 
     def close(self):
         if self.h:

@@ -376,6 +376,81 @@ def build_candidates_in(arena, controls, method, now):
     return ci
 
 
+class Ami(C.Structure):
+    _fields_ = [("id", C.c_char_p), ("requirements", Requirements)]
+
+
+class NodeClassStatus(C.Structure):
+    _fields_ = [("hash", C.c_char_p), ("hash_version", C.c_char_p), ("amis", C.POINTER(Ami)),
+                ("subnets", C.POINTER(C.c_char_p)), ("security_groups", C.POINTER(C.c_char_p)),
+                ("capacity_reservations", C.POINTER(C.c_char_p)), ("n_amis", C.c_uint32), ("n_subnets", C.c_uint32),
+                ("n_security_groups", C.c_uint32), ("n_capacity_reservations", C.c_uint32)]
+
+
+class PoolDrift(C.Structure):
+    _fields_ = [("nodeclass", C.c_int32), ("reserved_", C.c_int32), ("hash", C.c_char_p), ("hash_version", C.c_char_p)]
+
+
+class NodeDriftIn(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("n_security_groups", C.c_uint32), ("nodepool_hash", C.c_char_p),
+                ("nodepool_hash_version", C.c_char_p), ("nodeclass_hash", C.c_char_p),
+                ("nodeclass_hash_version", C.c_char_p), ("image_id", C.c_char_p), ("subnet_id", C.c_char_p),
+                ("security_groups", C.POINTER(C.c_char_p)), ("capacity_reservation_id", C.c_char_p)]
+
+
+class DriftIn(C.Structure):
+    _fields_ = [("nodeclasses", C.POINTER(NodeClassStatus)), ("pools", C.POINTER(PoolDrift)),
+                ("nodes", C.POINTER(NodeDriftIn)), ("n_nodeclasses", C.c_uint32), ("n_pools", C.c_uint32),
+                ("n_nodes", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+# enum kp_drift_status, kp_drift_reason; KP_DRIFT_HAS_INSTANCE
+(DRIFT_OK, DRIFT_SKIP_NOT_MANAGED, DRIFT_SKIP_NO_NODECLASS, DRIFT_ERR_INSTANCE, DRIFT_ERR_INSTANCE_TYPE,
+ DRIFT_ERR_NO_AMIS, DRIFT_ERR_NO_SECURITY_GROUPS, DRIFT_ERR_NO_SUBNETS) = range(8)
+DRIFT_STATUS_NAMES = ("OK", "SKIP_NOT_MANAGED", "SKIP_NO_NODECLASS", "ERR_INSTANCE", "ERR_INSTANCE_TYPE", "ERR_NO_AMIS",
+                      "ERR_NO_SECURITY_GROUPS", "ERR_NO_SUBNETS")
+(DRIFT_NONE, DRIFT_NODEPOOL, DRIFT_REQUIREMENTS, DRIFT_NODECLASS, DRIFT_AMI, DRIFT_SECURITY_GROUP, DRIFT_SUBNET,
+ DRIFT_CAPACITY_RESERVATION) = range(8)
+DRIFT_REASON_NAMES = ("", "NodePoolDrift", "RequirementsDrift", "NodeClassDrift", "AMIDrift", "SecurityGroupDrift",
+                      "SubnetDrift", "CapacityReservationDrift")
+DRIFT_REASON_COUNT = 8
+DRIFT_HAS_INSTANCE = 1
+DRIFT_NO_AMI = 0xFFFFFFFF
+
+
+def node_drift_dtype():
+    """kp_node_drift"""
+    import numpy as np
+    return np.dtype([("reason", "<i4"), ("status", "<i4"), ("detail", "<u4"), ("r", "<u4")])
+
+
+def build_drift_in(arena, inputs):
+    """kpamd.model.DriftInputs -> kp_drift_in (buffers kept by the arena)."""
+    def ids(xs):
+        return arena.arr(C.c_char_p, [arena.s(x) for x in xs]) if xs else None
+
+    ncs = []
+    for nc in inputs.nodeclasses:
+        amis = arena.arr(Ami, [Ami(arena.s(a.id), arena.requirements(a.requirements)) for a in nc.amis])
+        ncs.append(NodeClassStatus(arena.s(nc.hash), arena.s(nc.hash_version), amis if nc.amis else None,
+                                   ids(nc.subnets), ids(nc.security_groups), ids(nc.capacity_reservations),
+                                   len(nc.amis), len(nc.subnets), len(nc.security_groups),
+                                   len(nc.capacity_reservations)))
+    pools = [PoolDrift(int(p.nodeclass), 0, arena.s(p.hash), arena.s(p.hash_version)) for p in inputs.pools]
+    nodes = []
+    for n in inputs.nodes:
+        i = n.instance
+        nodes.append(NodeDriftIn(DRIFT_HAS_INSTANCE if i is not None else 0, len(i.security_groups) if i else 0,
+                                 arena.s(n.nodepool_hash), arena.s(n.nodepool_hash_version), arena.s(n.nodeclass_hash),
+                                 arena.s(n.nodeclass_hash_version), arena.s(i.image_id) if i else None,
+                                 arena.s(i.subnet_id) if i else None, ids(i.security_groups) if i else None,
+                                 arena.s(i.capacity_reservation_id) if i else None))
+    di = DriftIn(arena.arr(NodeClassStatus, ncs) if ncs else None, arena.arr(PoolDrift, pools) if pools else None,
+                 arena.arr(NodeDriftIn, nodes) if nodes else None, len(ncs), len(pools), len(nodes), 0)
+    arena.keep.append(di)
+    return di
+
+
 # enum kp_validity
 (VALID, INVALID_UNSCHEDULED, INVALID_NO_REPLACEMENT_NEEDED, INVALID_MULTIPLE, INVALID_NEEDS_REPLACEMENT,
  INVALID_NOT_SUBSET, INVALID_BUDGET) = range(7)

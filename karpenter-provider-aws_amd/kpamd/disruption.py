@@ -30,6 +30,9 @@ CS3 and R:website/content/en/preview/concepts/disruption.md:89-128):
                                             DisruptionControls: per node the reason it is no candidate (do-not-disrupt,
                                             PDBs, consolidateAfter, ...), the costs, and the candidates in disruption
                                             order; Controller.compute_command takes its lists from it then
+  detect_drift(cluster, plan, now)          IsDrifted for every node on the device (kp_cluster_detect_drift) when the
+                                            cluster carries DriftInputs, and the Drifted condition's life applied to
+                                            ClusterNode.drifted; Controller.compute_command calls it first then
   Validation(cluster, plan)                 Validation.IsValid of a computed command against a FRESH snapshot (upstream
   Controller.validate(cmd, old, new, plan)  disruption/validation.go, restated in DESIGN §12): the candidates mapped by
                                             node name (gone, deleting, nominated, the budget walk), then one
@@ -313,6 +316,30 @@ def drift_order(cluster):
     return sorted(idx, key=lambda i: (cluster.nodes[i].drifted, cluster.nodes[i].node.name))
 
 
+def detect_drift(cluster, plan, now):
+    """Drift detection for every node of the snapshot (cluster.drift_inputs) and the life of the Drifted
+    condition (R:website/content/en/preview/concepts/disruption.md:162-164), applied to ClusterNode.drifted and, when
+    the cluster has controls, to controls.nodes[i].drifted: a newly drifted node gets `now`, a node still drifted keeps
+    its time, a node no longer drifted loses it; a node whose status is an error keeps what it had (upstream returns
+    the error and does not touch the condition). plan: the resident snapshot (ClusterPlan, or any object with the same
+    detect_drift()). Returns (records, counts)."""
+    if cluster.drift_inputs is None:
+        raise ValueError("the cluster carries no DriftInputs")
+    records, counts = plan.detect_drift()[:2]
+    controls = getattr(cluster, "controls", None)
+    at = _ts(now)
+    for i, node in enumerate(cluster.nodes):
+        if int(records[i]["status"]) >= abi.DRIFT_ERR_INSTANCE:
+            continue
+        if int(records[i]["reason"]) == abi.DRIFT_NONE:
+            node.drifted = None
+        elif node.drifted is None:
+            node.drifted = at
+        if controls is not None:
+            controls.nodes[i].drifted = None if node.drifted is None else int(node.drifted)
+    return records, counts
+
+
 class Drift:
     """Drift (upstream disruption/drift.go v1.5.1, restated in DESIGN §10). Budgets are asked with the reason Drifted.
     Drifted candidates without reschedulable pods come first: each whose pool still has allowance is kept (one
@@ -376,6 +403,8 @@ class Controller:
         return Command(method, candidates, r["decision"], out)
 
     def compute_command(self, cluster, plan, now=None, not_ready=(), extra_deleting=None):
+        if getattr(cluster, "drift_inputs", None) is not None:  # which nodes are drifted is computed, not given
+            detect_drift(cluster, plan, now)
         if getattr(cluster, "controls", None) is not None:
             return self._compute_with_controls(cluster, plan, now, not_ready, extra_deleting)
         cands = candidate_order(cluster)

@@ -192,6 +192,62 @@ class DisruptionControls:
 
 
 @dataclass
+class AMI:
+    """One entry of EC2NodeClass status.amis: the image id and the requirements an instance type must be compatible with."""
+    id: str
+    requirements: List[Req] = field(default_factory=list)
+
+
+@dataclass
+class NodeClassStatus:
+    """EC2NodeClass as drift detection reads it (R:pkg/cloudprovider/drift.go): the ec2nodeclass-hash annotations
+    (None: absent) and the status lists, amis in status order."""
+    amis: List[AMI] = field(default_factory=list)
+    subnets: List[str] = field(default_factory=list)
+    security_groups: List[str] = field(default_factory=list)
+    capacity_reservations: List[str] = field(default_factory=list)
+    hash: Optional[str] = None
+    hash_version: Optional[str] = None
+
+
+@dataclass
+class InstanceInfo:
+    """The EC2 instance behind a NodeClaim's provider id."""
+    image_id: str
+    subnet_id: str
+    security_groups: List[str] = field(default_factory=list)
+    capacity_reservation_id: Optional[str] = None
+
+
+@dataclass
+class PoolDrift:
+    """A NodePool's side of drift detection: the index of its EC2NodeClass in DriftInputs.nodeclasses (-1: no
+    nodeClassRef, or unresolved) and its karpenter.sh/nodepool-hash annotations (None: absent)."""
+    nodeclass: int = -1
+    hash: Optional[str] = None
+    hash_version: Optional[str] = None
+
+
+@dataclass
+class NodeDrift:
+    """A NodeClaim's side: its four hash annotations (None: absent) and its instance (None: no provider id / no record)."""
+    nodepool_hash: Optional[str] = None
+    nodepool_hash_version: Optional[str] = None
+    nodeclass_hash: Optional[str] = None
+    nodeclass_hash_version: Optional[str] = None
+    instance: Optional[InstanceInfo] = None
+
+
+@dataclass
+class DriftInputs:
+    """The inputs of drift detection (kp_cluster_detect_drift): pools indexed like Cluster.nodepools, nodes like
+    Cluster.nodes."""
+    nodeclasses: List[NodeClassStatus]
+    pools: List[PoolDrift]
+    nodes: List[NodeDrift]
+
+
+@dataclass
 class Cluster:
     catalogs: List[List[InstanceType]]
     nodepools: List[NodePool]
@@ -207,6 +263,7 @@ class Cluster:
     namespaces: Dict[str, Dict[str, str]] = field(default_factory=dict)  # cluster namespaces: name -> labels
     pod_uid_str: Optional[List[str]] = None  # metadata.uid per pod (kp_cluster.pod_uids): the exact Queue tie-break
     controls: Optional[DisruptionControls] = None  # None: not modelled (candidate_order / drift_order decide)
+    drift_inputs: Optional[DriftInputs] = None     # None: not modelled (ClusterNode.drifted is given)
 
 
 @dataclass

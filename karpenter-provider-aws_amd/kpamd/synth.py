@@ -819,3 +819,132 @@ def add_disruption_controls(cluster, seed, n_pdbs=12, now=1_750_100_000):
                                                  [0, 0, 1, 3][int(rng.integers(0, 4))]))
     cluster.controls = controls
     return controls
+
+
+# ------------------------------------------------------------------------------------------------
+# drift detection inputs (kp_cluster_detect_drift)
+# ------------------------------------------------------------------------------------------------
+def ami_for_type(it, amis):
+    """Index of the first AMI of `amis` whose requirements the type is compatible with (MapToInstanceTypes for one type),
+    or None. Handles what a catalogue type carries (one In or DoesNotExist requirement per key) against AMI
+    requirements that name a key once: the forms add_drift_inputs and the end-to-end model generate. The tests hold
+    it to the oracle."""
+    held = {r[0]: set(r[2]) if r[1] == "In" else set() for r in it.requirements}
+
+    def meets(key, op, values):
+        if key not in held:
+            return op in ("NotIn", "DoesNotExist")
+        s = held[key]
+        if op == "In":
+            return bool(s & set(values))
+        if op == "NotIn":
+            return bool(s - set(values)) or not s
+        if op == "Exists":
+            return bool(s)
+        if op == "DoesNotExist":
+            return not s
+        bound = int(values[0])
+        ints = [int(v) for v in s if v.lstrip("+-").isdigit()]
+        return any(v > bound if op == "Gt" else v < bound for v in ints)
+
+    for i, a in enumerate(amis):
+        if all(meets(r[0], r[1], list(r[2])) for r in a.requirements):
+            return i
+    return None
+
+
+def add_drift_inputs(cluster, seed, n_nodeclasses=4, n_amis=8, errors=True):
+    """Randomized DriftInputs for `cluster` (set as cluster.drift_inputs and returned); the cluster itself is not
+    changed. n_nodeclasses EC2NodeClasses of n_amis AMIs each (nvidia, neuron and per-architecture standard AMIs in
+    either order, the rest fillers that match a single instance type or nothing), a subnet per zone, one to three
+    security groups, two capacity reservations and the hash annotations; pool p uses nodeclass p mod n_nodeclasses.
+    With errors and at least six pools, the last four pools get no nodeclass and nodeclasses without AMIs, without
+    security groups and without subnets. Every node is launched clean (the AMI its type maps to, a subnet and the
+    security groups of its nodeclass, in a shuffled order with a duplicate, equal hashes), then each check is broken
+    for a few percent of the nodes: a changed, missing or re-versioned hash on either level, no instance, a stale or
+    foreign image, a security group more, fewer or different, a foreign subnet, a reservation that is or is not
+    selected."""
+    from .model import AMI, DriftInputs, InstanceInfo, NodeClassStatus, NodeDrift, PoolDrift
+    rng = np.random.default_rng(seed)
+    names = sorted({it.name for c in cluster.catalogs for it in c})
+    gpu, accel = K + "instance-gpu-count", K + "instance-accelerator-count"
+    classes = []
+    for c in range(n_nodeclasses):
+        amis = [AMI(f"ami-{c}-nvidia", [("kubernetes.io/arch", "In", ["amd64"]), (gpu, "Exists", [])]),
+                AMI(f"ami-{c}-neuron", [("kubernetes.io/arch", "In", ["amd64"]), (accel, "Exists", [])]),
+                AMI(f"ami-{c}-amd64", [("kubernetes.io/arch", "In", ["amd64"]), (gpu, "DoesNotExist", []),
+                                       (accel, "DoesNotExist", [])]),
+                AMI(f"ami-{c}-arm64", [("kubernetes.io/arch", "In", ["arm64"])])]
+        if rng.random() < 0.5:  # the general AMIs first: they win for every type
+            amis = amis[2:] + amis[:2]
+        for f in range(max(0, n_amis - 4)):
+            form = int(rng.integers(0, 4))
+            name = names[int(rng.integers(0, len(names)))]
+            reqs = [[("node.kubernetes.io/instance-type", "In", [name])],
+                    [("node.kubernetes.io/instance-type", "In", ["no.such"])],
+                    [("example.com/custom", "Exists", [])],
+                    [(K + "instance-cpu", "Gt", ["100000"]), (K + "instance-family", "NotIn", ["m5"])]][form]
+            amis.insert(int(rng.integers(0, len(amis) + 1)), AMI(f"ami-{c}-filler{f}", reqs))
+        classes.append(NodeClassStatus(amis[:max(n_amis, 1)], [f"subnet-{c}-{z}" for z in range(len(ZONES))],
+                                       [f"sg-{c}-{g}" for g in range(int(rng.integers(1, 4)))],
+                                       [f"cr-{c}-0", f"cr-{c}-1"], f"class-hash-{c}", "v1"))
+    n_pools = len(cluster.nodepools)
+    pools = [PoolDrift(p % n_nodeclasses, f"pool-hash-{p}", "v1") for p in range(n_pools)]
+    if errors and n_pools >= 6:
+        pools[-4].nodeclass = -1
+        for j, gone in enumerate(("amis", "security_groups", "subnets")):
+            src = classes[j % n_nodeclasses]
+            broken = NodeClassStatus(list(src.amis), list(src.subnets), list(src.security_groups),
+                                     list(src.capacity_reservations), src.hash, src.hash_version)
+            setattr(broken, gone, [])
+            pools[-3 + j].nodeclass = len(classes)
+            classes.append(broken)
+    pool_of = {p.name: i for i, p in enumerate(cluster.nodepools)}
+    nodes = []
+    for n in cluster.nodes:
+        p = pool_of.get(n.node.labels.get("karpenter.sh/nodepool"))
+        if p is None or pools[p].nodeclass < 0:
+            nodes.append(NodeDrift("x", "v1", "y", "v1", InstanceInfo("ami-any", "subnet-any", ["sg-any"])))
+            continue
+        nc = classes[pools[p].nodeclass]
+        it = cluster.catalogs[n.catalog][n.instance_type]
+        m = ami_for_type(it, nc.amis)
+        zone = n.node.labels.get("topology.kubernetes.io/zone")
+        z = ZONES.index(zone) if zone in ZONES else 0
+        sgs = list(nc.security_groups) or ["sg-own"]
+        sgs = [sgs[i] for i in rng.permutation(len(sgs))] + [sgs[0]]
+        inst = InstanceInfo(nc.amis[m].id if m is not None else "ami-unmapped",
+                            nc.subnets[z % len(nc.subnets)] if nc.subnets else "subnet-own", sgs)
+        d = NodeDrift(pools[p].hash, pools[p].hash_version, nc.hash, nc.hash_version, inst)
+        r = rng.random(10)
+        if r[0] < 0.04:
+            d.nodepool_hash = "pool-hash-old"
+        elif r[0] < 0.06:
+            d.nodepool_hash = None
+        elif r[0] < 0.08:
+            d.nodepool_hash, d.nodepool_hash_version = "pool-hash-old", "v0"
+        if r[1] < 0.04:
+            d.nodeclass_hash = "class-hash-old"
+        elif r[1] < 0.06:
+            d.nodeclass_hash_version = None
+        elif r[1] < 0.08:
+            d.nodeclass_hash, d.nodeclass_hash_version = "class-hash-old", "v0"
+        if r[2] < 0.02:
+            d.instance = None
+        if r[3] < 0.03:
+            inst.image_id = "ami-stale"
+        elif r[3] < 0.06:
+            inst.image_id = nc.amis[int(rng.integers(0, len(nc.amis)))].id if nc.amis else "ami-stale"
+        if r[4] < 0.02:
+            inst.security_groups = sgs + ["sg-extra"]
+        elif r[4] < 0.04:
+            inst.security_groups = sgs[1:-1] if len(nc.security_groups) > 1 else ["sg-other"]
+        if r[5] < 0.04:
+            inst.subnet_id = "subnet-gone"
+        if r[6] < 0.15:
+            inst.capacity_reservation_id = f"cr-{pools[p].nodeclass}-{int(rng.integers(0, 2))}"
+        elif r[6] < 0.19:
+            inst.capacity_reservation_id = "cr-released"
+        nodes.append(d)
+    cluster.drift_inputs = DriftInputs(classes, pools, nodes)
+    return cluster.drift_inputs
