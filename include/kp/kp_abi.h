@@ -1433,6 +1433,102 @@ typedef struct kp_node_drift {
 int32_t kp_cluster_detect_drift(kp_cluster_plan* plan, const kp_drift_in* in, kp_node_drift* out /* n_nodes */,
                                 uint64_t* counts /* KP_DRIFT_REASON_COUNT words, may be NULL */,
                                 kp_solve_stats* stats);
+
+/* The scheduler's inputs (upstream NewScheduler's getDaemonOverhead, remainingResources, StateNode.Available() and the
+ * ExistingNode's remaining daemonset requests), additive to ABI v13. One call computes, from cluster
+ * state, the four inputs every Solve and cluster plan takes: kp_nodepool.daemon_requests, kp_nodepool.limits (the
+ * remainder), kp_existing_node.available and kp_existing_node.requests. Upstream core (scheduler.go, existingnode.go,
+ * statenode.go) is not among the references: the rule below is RESTATED and parity beyond it is unpinned. The pinned
+ * piece is the per-template rule where a daemonset has at most one required term, no preferred term, and the template
+ * no PreferNoSchedule taint: there it equals R:test/pkg/environment/common/expectations.go:1100-1140 ("the same logic
+ * as the scheduler"; documented at R:website/content/en/preview/faq.md:105-108).
+ *
+ * Inputs. nodepools are kp_nodepool as a Solve takes them, except that limits holds spec.limits (not the remainder)
+ * and daemon_requests is ignored. daemonsets are the DaemonSets' pod templates; of a kp_pod_shape only requests,
+ * node_selector, required_terms, preferred_terms (ignored: strict requirements hold no preferences), tolerations and
+ * volume_requirements are read. nodes carry labels, taints, allocatable and capacity; pod_offsets is the CSR of the
+ * pods bound to each node, each pod an index into request_rows (the distinct request lists, `pods` included as
+ * kp_pod_shape.requests has it) and KP_SCHED_POD_DAEMON when a DaemonSet owns it. The caller decides which nodes and
+ * pods it lists (upstream: the active nodes; a node being deleted is not listed).
+ *
+ * strict(d, i) = d's node selector + its i-th required term + its volume requirements (NewStrictPodRequirements is
+ * strict(d, 0); with no required term, the selector and the volume requirements alone).
+ *
+ * A template d is compatible with a NODE when every taint of the node is tolerated by some toleration of d
+ * (Toleration.ToleratesTaint; PreferNoSchedule taints count), and NewLabelRequirements(node labels).Compatible(
+ * strict(d, 0)) holds, undefined well-known labels NOT allowed: a key the node does not carry passes only under NotIn
+ * or DoesNotExist.
+ * A template d is compatible with a NodePool's TEMPLATE (upstream isDaemonPodCompatible) when every taint of the
+ * NodePool other than PreferNoSchedule ones is tolerated by d, and for some i, tried in order (Preferences.Relax drops
+ * the first required term on each failure), template.Requirements.Compatible(strict(d, i)) holds with undefined
+ * well-known labels allowed. The template's requirements are NewNodeClaimTemplate's: the pool's requirements, its
+ * labels, and karpenter.sh/nodepool In {name}.
+ *
+ * Per node:  available    = allocatable - sum of the requests of every bound pod, for the resources present in
+ *                           allocatable (resources.Subtract keeps the left side's keys); may be negative
+ *            requests     = for each resource present in some compatible template:
+ *                           max(0, sum over compatible templates - sum over the bound pods with KP_SCHED_POD_DAEMON)
+ *            n_compatible = the number of compatible templates; compat (optional) holds them as bits, template d at
+ *                           bit d % 64 of word d / 64, max(1, ceil(n_daemonsets / 64)) words per node
+ * Per pool:  daemon_requests = sum over the templates compatible with the pool's template (present: their union)
+ *            remaining    = limits - sum of capacity over the nodes whose karpenter.sh/nodepool label names the pool
+ *                           (the first pool of that name), for the resources present in limits; may be negative; a
+ *                           pool without limits stays unlimited (present = 0); a node naming no pool counts nowhere
+ *            n_compatible
+ * A resource absent from a list counts 0. Sums are int64 milli-units and wrap on overflow.
+ *
+ * ctx == NULL validates the state on the host and writes nothing (kp_solve_validate's convention). Errors: KP_E_INVAL
+ * for a NULL state or out, a NULL array whose count is not 0, NULL out->nodes / out->pools with n_nodes / n_nodepools
+ * not 0, pod_offsets that do not start at 0, decrease, or end elsewhere than n_pods, a request row >= n_request_rows,
+ * an unknown requirement / toleration operator, a NULL NodePool name, label key, taint key or requirement key or
+ * value. KP_E_UNSUPPORTED for 65,535 or more NodePools and 2^31 or more request rows. stats: device_ms (the kernels),
+ * host_ms (the call), prepare_ms (the host compile, part of host_ms). */
+#define KP_SCHED_POD_DAEMON 1u
+typedef struct kp_sched_pod {
+  uint32_t requests;                  /* index into kp_sched_state.request_rows */
+  uint32_t flags;                     /* KP_SCHED_POD_DAEMON */
+} kp_sched_pod;
+typedef struct kp_sched_node {
+  const kp_label* labels;
+  const kp_taint* taints;
+  uint32_t n_labels;
+  uint32_t n_taints;
+  kp_resource_list allocatable;
+  kp_resource_list capacity;
+} kp_sched_node;
+typedef struct kp_sched_state {
+  const kp_nodepool* nodepools;
+  const kp_pod_shape* daemonsets;
+  const kp_sched_node* nodes;
+  const uint32_t* pod_offsets;        /* n_nodes + 1 */
+  const kp_sched_pod* pods;
+  const kp_resource_list* request_rows;
+  uint32_t n_nodepools;
+  uint32_t n_daemonsets;
+  uint32_t n_nodes;
+  uint32_t n_pods;
+  uint32_t n_request_rows;
+  uint32_t reserved_;
+} kp_sched_state;
+typedef struct kp_sched_node_out {
+  kp_resource_list available;         /* -> kp_existing_node.available */
+  kp_resource_list requests;          /* -> kp_existing_node.requests */
+  uint32_t n_compatible;
+  uint32_t reserved_;
+} kp_sched_node_out;
+typedef struct kp_sched_pool_out {
+  kp_resource_list daemon_requests;   /* -> kp_nodepool.daemon_requests */
+  kp_resource_list remaining;         /* -> kp_nodepool.limits */
+  uint32_t n_compatible;
+  uint32_t reserved_;
+} kp_sched_pool_out;
+typedef struct kp_sched_out {         /* caller-allocated */
+  kp_sched_node_out* nodes;           /* n_nodes */
+  kp_sched_pool_out* pools;           /* n_nodepools */
+  uint64_t* compat;                   /* n_nodes * max(1, ceil(n_daemonsets / 64)) words, or NULL */
+} kp_sched_out;
+int32_t kp_scheduler_inputs(kp_ctx* ctx, const kp_sched_state* state, kp_sched_out* out, kp_solve_stats* stats);
+
 /* The reduction kp_consolidate_argmin applies to the gathered per-rank records (host-only; exposed for callers that
  * reduce over another transport, and for tests): counts are summed, the best record wins. */
 int32_t kp_choice_reduce(const kp_choice* per_rank, uint32_t n, kp_choice* out);

@@ -33,6 +33,7 @@
 #include "kp/kp_abi.h"
 #include "kp_cand.h"
 #include "kp_driftdet.h"
+#include "kp_schedin.h"
 #include "kp_device.h"
 #include "kp_model.h"
 
@@ -226,6 +227,9 @@ struct kp_ctx {
   // per-Solve device arena handed back by kp_solve_plan_destroy and reused by the next kp_solve_prepare
   void* spare = nullptr;
   size_t spare_bytes = 0;
+  // kp_scheduler_inputs' device arena, kept across calls (grown, never shrunk)
+  void* schedin = nullptr;
+  size_t schedin_bytes = 0;
   // kp_ctx_destroy's reference plus one per live dependent (catalogue, plan, communicator): the context is freed
   // when the last goes, so a dependent may be destroyed after the context (any order, e.g. a garbage collector's)
   std::atomic<int> refs{1};
@@ -234,6 +238,7 @@ static void CtxFree(kp_ctx* c) {
   (void)hipSetDevice(c->device);
   c->bases.clear();
   if (c->spare) (void)hipFree(c->spare);
+  if (c->schedin) (void)hipFree(c->schedin);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->ev2) (void)hipEventDestroy(c->ev2);
@@ -8848,6 +8853,285 @@ int32_t kp_cluster_detect_drift(kp_cluster_plan* plan, const kp_drift_in* in, kp
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     stats->device_ms = ms;
+    stats->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return KP_OK;
+}
+
+}  // extern "C"
+
+// ---- The scheduler's inputs (kp_scheduler_inputs) -------------------------------------------------------------------
+// The host does strings only: the templates' strict requirements merged per key (SReq), the nodes' label values as ids
+// of per-key dictionaries (key-major, as DriftBuild's node_val), one bitset per (template, key), the distinct taint
+// sets against the templates' tolerations, and the P x D template side with its relax loop. Every sum is the device's
+// (kp_schedin.hip).
+static_assert(sizeof(SiNodeOut) == sizeof(kp_sched_node_out) && sizeof(SiPoolOut) == sizeof(kp_sched_pool_out),
+              "the device records mirror the ABI's");
+
+namespace {
+// Requirements.Compatible(q) on merged string requirements (oracle.cpp Compatible + Intersects)
+bool SCompatible(const std::map<string, SReq>& r, const std::map<string, SReq>& q, bool allow_undefined_wellknown) {
+  for (auto& kv : q) {
+    auto it = r.find(kv.first);
+    if (it == r.end()) {
+      if (kv.second.NegOp() || (allow_undefined_wellknown && WellKnown().count(kv.first))) continue;
+      return false;
+    }
+    const SReq m = SReqMerge(it->second, kv.second);
+    if (!m.complement && m.values.empty() && !(kv.second.NegOp() && it->second.NegOp())) return false;
+  }
+  return true;
+}
+void AddLabel(std::map<string, SReq>& into, const kp_label& l) {
+  SReq q;
+  q.values.insert(l.value ? l.value : "");
+  auto ins = into.emplace(Normalize(l.key), q);
+  if (!ins.second) ins.first->second = SReqMerge(q, ins.first->second);
+}
+// strict(d, i): the node selector, the i-th required term (if any) and the volume requirements
+void StrictReqs(const kp_pod_shape& d, uint32_t i, std::map<string, SReq>& out) {
+  for (uint32_t j = 0; j < d.n_node_selector; j++) AddLabel(out, d.node_selector[j]);
+  if (i < d.n_required_terms) MergeReqs(d.required_terms[i], out);
+  MergeReqs(kp_requirements{d.volume_requirements, d.n_volume_requirements, 0}, out);
+}
+bool ToleratesTaintT(const kp_toleration& t, const TaintT& taint) {  // corev1 Toleration.ToleratesTaint
+  if (t.effect != KP_EFFECT_ANY && t.effect != taint.effect) return false;
+  if (t.key && *t.key && taint.key != t.key) return false;
+  if (t.op == KP_TOL_EQUAL) return taint.value == (t.value ? t.value : "");
+  return t.op == KP_TOL_EXISTS;
+}
+bool ToleratesAllT(const kp_pod_shape& d, const vector<TaintT>& taints, bool skip_pns) {
+  for (const TaintT& taint : taints) {
+    if (skip_pns && taint.effect == KP_EFFECT_PREFER_NO_SCHEDULE) continue;
+    bool ok = false;
+    for (uint32_t j = 0; j < d.n_tolerations && !ok; j++) ok = ToleratesTaintT(d.tolerations[j], taint);
+    if (!ok) return false;
+  }
+  return true;
+}
+int32_t TaintsOf(const kp_taint* t, uint32_t n, const char* who, uint32_t i, vector<TaintT>& out) {
+  if (n && !t) return fail(KP_E_INVAL, "%s %u: null taints", who, i);
+  for (uint32_t j = 0; j < n; j++) {
+    if (!t[j].key) return fail(KP_E_INVAL, "%s %u: null taint key", who, i);
+    out.push_back({t[j].key, t[j].value ? t[j].value : "", t[j].effect});
+  }
+  std::sort(out.begin(), out.end());
+  return KP_OK;
+}
+int32_t CheckLabels(const kp_label* l, uint32_t n, const char* who, uint32_t i) {
+  if (n && !l) return fail(KP_E_INVAL, "%s %u: null labels", who, i);
+  for (uint32_t j = 0; j < n; j++)
+    if (!l[j].key) return fail(KP_E_INVAL, "%s %u: null label key", who, i);
+  return KP_OK;
+}
+int32_t SchedInValidate(const kp_sched_state* st, const kp_sched_out* out) {
+  if (!st || !out) return fail(KP_E_INVAL, "null state or out");
+  if ((st->n_nodepools && !st->nodepools) || (st->n_daemonsets && !st->daemonsets) || (st->n_nodes && !st->nodes) ||
+      (st->n_pods && !st->pods) || (st->n_request_rows && !st->request_rows) || (st->n_nodes && !st->pod_offsets))
+    return fail(KP_E_INVAL, "null nodepools, daemonsets, nodes, pod_offsets, pods or request_rows");
+  if ((st->n_nodes && !out->nodes) || (st->n_nodepools && !out->pools)) return fail(KP_E_INVAL, "null out->nodes or out->pools");
+  if (st->n_nodepools >= 0xFFFF) return fail(KP_E_UNSUPPORTED, "%u NodePools (max 65534)", st->n_nodepools);
+  if (st->n_request_rows >= (1u << 31)) return fail(KP_E_UNSUPPORTED, "%u request rows (max 2^31 - 1)", st->n_request_rows);
+  if (st->n_nodes) {
+    if (st->pod_offsets[0] != 0) return fail(KP_E_INVAL, "pod_offsets[0] = %u", st->pod_offsets[0]);
+    for (uint32_t i = 0; i < st->n_nodes; i++)
+      if (st->pod_offsets[i + 1] < st->pod_offsets[i]) return fail(KP_E_INVAL, "pod_offsets decrease at node %u", i);
+    if (st->pod_offsets[st->n_nodes] != st->n_pods)
+      return fail(KP_E_INVAL, "pod_offsets end at %u, n_pods = %u", st->pod_offsets[st->n_nodes], st->n_pods);
+  } else if (st->n_pods) {
+    return fail(KP_E_INVAL, "%u pods and no node", st->n_pods);
+  }
+  for (uint32_t i = 0; i < st->n_pods; i++)
+    if (st->pods[i].requests >= st->n_request_rows)
+      return fail(KP_E_INVAL, "pod %u: request row %u of %u", i, st->pods[i].requests, st->n_request_rows);
+  for (uint32_t p = 0; p < st->n_nodepools; p++) {
+    const kp_nodepool& np = st->nodepools[p];
+    if (!np.name) return fail(KP_E_INVAL, "NodePool %u: null name", p);
+    if (int32_t rc = CheckReqs(np.requirements, "NodePool", p, 0)) return rc;
+    if (int32_t rc = CheckLabels(np.labels, np.n_labels, "NodePool", p)) return rc;
+  }
+  for (uint32_t d = 0; d < st->n_daemonsets; d++) {
+    const kp_pod_shape& sh = st->daemonsets[d];
+    if (int32_t rc = CheckLabels(sh.node_selector, sh.n_node_selector, "daemonset", d)) return rc;
+    if ((sh.n_required_terms && !sh.required_terms) || (sh.n_tolerations && !sh.tolerations) ||
+        (sh.n_volume_requirements && !sh.volume_requirements))
+      return fail(KP_E_INVAL, "daemonset %u: null required terms, tolerations or volume requirements", d);
+    for (uint32_t j = 0; j < sh.n_required_terms; j++)
+      if (int32_t rc = CheckReqs(sh.required_terms[j], "daemonset", d, j)) return rc;
+    if (int32_t rc = CheckReqs(kp_requirements{sh.volume_requirements, sh.n_volume_requirements, 0}, "daemonset volumes", d, 0))
+      return rc;
+    for (uint32_t j = 0; j < sh.n_tolerations; j++)
+      if (sh.tolerations[j].op != KP_TOL_EQUAL && sh.tolerations[j].op != KP_TOL_EXISTS)
+        return fail(KP_E_INVAL, "daemonset %u: toleration operator %d", d, sh.tolerations[j].op);
+  }
+  for (uint32_t i = 0; i < st->n_nodes; i++)
+    if (int32_t rc = CheckLabels(st->nodes[i].labels, st->nodes[i].n_labels, "node", i)) return rc;
+  return KP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t kp_scheduler_inputs(kp_ctx* ctx, const kp_sched_state* st, kp_sched_out* out, kp_solve_stats* stats) {
+  if (int32_t rc = SchedInValidate(st, out)) return rc;
+  const uint32_t N = st->n_nodes, D = st->n_daemonsets, P = st->n_nodepools, R = st->n_request_rows;
+  vector<vector<TaintT>> pool_taints(P), node_taints(N);
+  for (uint32_t p = 0; p < P; p++)
+    if (int32_t rc = TaintsOf(st->nodepools[p].taints, st->nodepools[p].n_taints, "NodePool", p, pool_taints[p])) return rc;
+  for (uint32_t i = 0; i < N; i++)
+    if (int32_t rc = TaintsOf(st->nodes[i].taints, st->nodes[i].n_taints, "node", i, node_taints[i])) return rc;
+  if (!ctx) return KP_OK;  // host-only validation
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  HIPCHK(hipSetDevice(ctx->device));
+  if (stats) memset(stats, 0, sizeof *stats);
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint32_t W = std::max<uint32_t>(1, (D + 63) / 64);
+  // the templates' strict requirements, their keys, the nodes' values under those keys
+  vector<std::map<string, SReq>> strict(D);
+  std::unordered_map<string, uint32_t> key_id;
+  for (uint32_t d = 0; d < D; d++) {
+    StrictReqs(st->daemonsets[d], 0, strict[d]);
+    for (auto& kv : strict[d]) key_id.emplace(kv.first, (uint32_t)key_id.size());
+  }
+  const uint32_t K = (uint32_t)key_id.size();
+  vector<std::unordered_map<string, uint32_t>> val_id(K);
+  vector<vector<string>> vals(K);
+  vector<uint32_t> node_val((size_t)K * N, SI_NONE), node_pool(N, SI_NONE), node_tset(std::max<uint32_t>(N, 1), 0);
+  vector<uint8_t> clash(K, 0);
+  std::unordered_map<string, uint32_t> pool_by_name;
+  for (uint32_t p = 0; p < P; p++) pool_by_name.emplace(st->nodepools[p].name, p);
+  std::map<vector<TaintT>, uint32_t> tset_id;
+  vector<const vector<TaintT>*> tsets;
+  for (uint32_t i = 0; i < N; i++) {
+    const kp_sched_node& n = st->nodes[i];
+    std::fill(clash.begin(), clash.end(), 0);
+    for (uint32_t j = 0; j < n.n_labels; j++) {
+      const string key = Normalize(n.labels[j].key), v = n.labels[j].value ? n.labels[j].value : "";
+      if (key == kNodePool) {
+        auto f = pool_by_name.find(v);
+        node_pool[i] = f == pool_by_name.end() ? SI_NONE : f->second;
+      }
+      auto f = key_id.find(key);
+      if (f == key_id.end()) continue;
+      const uint32_t k = f->second;
+      auto ins = val_id[k].emplace(v, (uint32_t)val_id[k].size());
+      if (ins.second) vals[k].push_back(v);
+      // two labels that normalize to one key with different values leave DoesNotExist: as a missing label
+      uint32_t& slot = node_val[(size_t)k * N + i];
+      if (clash[k] || (slot != SI_NONE && slot != ins.first->second)) clash[k] = 1, slot = SI_NONE;
+      else slot = ins.first->second;
+    }
+    auto ins = tset_id.emplace(node_taints[i], (uint32_t)tset_id.size());
+    if (ins.second) tsets.push_back(&ins.first->first);
+    node_tset[i] = ins.first->second;
+  }
+  // one bitset per (template, key) over the key's dictionary
+  vector<uint32_t> tk_off(D + 1, 0), tk_key, tk_bits;
+  vector<uint64_t> pass_bits;
+  for (uint32_t d = 0; d < D; d++) {
+    for (auto& kv : strict[d]) {
+      const uint32_t k = key_id[kv.first];
+      if (pass_bits.size() >= 0xFFFFFFFFull) return fail(KP_E_UNSUPPORTED, "the daemonsets' requirement bitsets are too large");
+      tk_key.push_back(k | (kv.second.NegOp() ? SI_ABSENT_PASSES : 0));
+      tk_bits.push_back((uint32_t)pass_bits.size());
+      const size_t base = pass_bits.size();
+      pass_bits.resize(base + std::max<size_t>(1, (vals[k].size() + 63) / 64), 0);
+      for (size_t v = 0; v < vals[k].size(); v++)
+        if (kv.second.Admits(vals[k][v])) pass_bits[base + (v >> 6)] |= 1ull << (v & 63);
+    }
+    tk_off[d + 1] = (uint32_t)tk_key.size();
+  }
+  // distinct taint set x template
+  const uint32_t S = std::max<uint32_t>(1, (uint32_t)tsets.size());
+  vector<uint64_t> tol_bits((size_t)S * W, 0);
+  for (uint32_t s = 0; s < tsets.size(); s++)
+    for (uint32_t d = 0; d < D; d++)
+      if (ToleratesAllT(st->daemonsets[d], *tsets[s], false)) tol_bits[(size_t)s * W + (d >> 6)] |= 1ull << (d & 63);
+  // the template side: P x D with the relax loop
+  vector<uint64_t> pool_compat((size_t)std::max<uint32_t>(P, 1) * W, 0);
+  for (uint32_t p = 0; p < P; p++) {
+    const kp_nodepool& np = st->nodepools[p];
+    std::map<string, SReq> tmpl;
+    MergeReqs(np.requirements, tmpl);
+    for (uint32_t j = 0; j < np.n_labels; j++) AddLabel(tmpl, np.labels[j]);
+    AddLabel(tmpl, kp_label{kNodePool, np.name});
+    for (uint32_t d = 0; d < D; d++) {
+      const kp_pod_shape& sh = st->daemonsets[d];
+      if (!ToleratesAllT(sh, pool_taints[p], true)) continue;
+      bool ok = SCompatible(tmpl, strict[d], true);
+      for (uint32_t i = 1; i < sh.n_required_terms && !ok; i++) {
+        std::map<string, SReq> q;
+        StrictReqs(sh, i, q);
+        ok = SCompatible(tmpl, q, true);
+      }
+      if (ok) pool_compat[(size_t)p * W + (d >> 6)] |= 1ull << (d & 63);
+    }
+  }
+  // the numbers
+  vector<kp_resource_list> alloc(std::max<uint32_t>(N, 1)), cap(std::max<uint32_t>(N, 1)), tmpl_req(std::max<uint32_t>(D, 1)),
+      limits(std::max<uint32_t>(P, 1));
+  for (uint32_t i = 0; i < N; i++) alloc[i] = st->nodes[i].allocatable, cap[i] = st->nodes[i].capacity;
+  for (uint32_t d = 0; d < D; d++) tmpl_req[d] = st->daemonsets[d].requests;
+  for (uint32_t p = 0; p < P; p++) limits[p] = st->nodepools[p].limits;
+  vector<uint32_t> pod(std::max<uint32_t>(st->n_pods, 1), 0), pod_off(N + 1, 0);
+  for (uint32_t i = 0; i < st->n_pods; i++)
+    pod[i] = st->pods[i].requests | ((st->pods[i].flags & KP_SCHED_POD_DAEMON) ? SI_POD_DAEMON : 0);
+  for (uint32_t i = 0; i <= N && N; i++) pod_off[i] = st->pod_offsets[i];
+  vector<uint32_t> pool_off(P + 1, 0), pool_nodes(std::max<uint32_t>(N, 1), 0);
+  for (uint32_t i = 0; i < N; i++)
+    if (node_pool[i] != SI_NONE) pool_off[node_pool[i] + 1]++;
+  for (uint32_t p = 0; p < P; p++) pool_off[p + 1] += pool_off[p];
+  {
+    vector<uint32_t> at(pool_off.begin(), pool_off.end() - 1);
+    for (uint32_t i = 0; i < N; i++)
+      if (node_pool[i] != SI_NONE) pool_nodes[at[node_pool[i]]++] = i;
+  }
+  Blob blob;
+  const size_t o_val = blob.put(node_val), o_tset = blob.put(node_tset), o_alloc = blob.put(alloc), o_cap = blob.put(cap),
+               o_poff = blob.put(pod_off), o_pod = blob.put(pod), o_rows = blob.put(st->request_rows, R),
+               o_tol = blob.put(tol_bits), o_tkoff = blob.put(tk_off), o_tkkey = blob.put(tk_key),
+               o_tkbits = blob.put(tk_bits), o_pass = blob.put(pass_bits), o_tmpl = blob.put(tmpl_req),
+               o_pooloff = blob.put(pool_off), o_poolnodes = blob.put(pool_nodes), o_pcompat = blob.put(pool_compat),
+               o_limits = blob.put(limits);
+  const size_t o_compat = blob.reserve_dev(sizeof(uint64_t) * std::max<size_t>((size_t)N * W, 1)),
+               o_nout = blob.reserve_dev(sizeof(SiNodeOut) * std::max<uint32_t>(N, 1)),
+               o_part = blob.reserve_dev(sizeof(int64_t) * KP_NUM_RESOURCES * SI_POOL_CHUNKS * std::max<uint32_t>(P, 1)),
+               o_pout = blob.reserve_dev(sizeof(SiPoolOut) * std::max<uint32_t>(P, 1));
+  if (blob.total() > ctx->schedin_bytes) {
+    if (ctx->schedin) (void)hipFree(ctx->schedin);
+    ctx->schedin = nullptr, ctx->schedin_bytes = 0;
+    HIPCHK(hipMalloc(&ctx->schedin, blob.total()));
+    ctx->schedin_bytes = blob.total();
+  }
+  uint8_t* base = (uint8_t*)ctx->schedin;
+  SchedInArgs a{};
+  a.n_nodes = (int)N, a.n_tmpl = (int)D, a.n_pools = (int)P, a.words = (int)W;
+  a.node_val = (const uint32_t*)(base + o_val), a.node_tset = (const uint32_t*)(base + o_tset);
+  a.alloc = (const kp_resource_list*)(base + o_alloc), a.cap = (const kp_resource_list*)(base + o_cap);
+  a.pod_off = (const uint32_t*)(base + o_poff), a.pod = (const uint32_t*)(base + o_pod);
+  a.rows = (const kp_resource_list*)(base + o_rows), a.tol_bits = (const uint64_t*)(base + o_tol);
+  a.tk_off = (const uint32_t*)(base + o_tkoff), a.tk_key = (const uint32_t*)(base + o_tkkey);
+  a.tk_bits = (const uint32_t*)(base + o_tkbits), a.pass_bits = (const uint64_t*)(base + o_pass);
+  a.tmpl = (const kp_resource_list*)(base + o_tmpl), a.pool_off = (const uint32_t*)(base + o_pooloff);
+  a.pool_nodes = (const uint32_t*)(base + o_poolnodes), a.pool_compat = (const uint64_t*)(base + o_pcompat);
+  a.limits = (const kp_resource_list*)(base + o_limits);
+  a.compat = (uint64_t*)(base + o_compat), a.node_out = (SiNodeOut*)(base + o_nout);
+  a.part = (int64_t*)(base + o_part), a.pool_out = (SiPoolOut*)(base + o_pout);
+  const double compile_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  hipStream_t s = ctx->stream;
+  HIPCHK(hipMemcpyAsync(base, blob.host.data(), blob.host.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(hipEventRecord(ctx->ev0, s));
+  HIPCHK(launch_scheduler_inputs(a, s));
+  HIPCHK(hipEventRecord(ctx->ev1, s));
+  if (N) HIPCHK(hipMemcpyAsync(out->nodes, a.node_out, sizeof(SiNodeOut) * N, hipMemcpyDeviceToHost, s));
+  if (P) HIPCHK(hipMemcpyAsync(out->pools, a.pool_out, sizeof(SiPoolOut) * P, hipMemcpyDeviceToHost, s));
+  if (N && out->compat) HIPCHK(hipMemcpyAsync(out->compat, a.compat, sizeof(uint64_t) * (size_t)N * W, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (stats) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    stats->device_ms = ms;
+    stats->prepare_ms = compile_ms;
     stats->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
   return KP_OK;

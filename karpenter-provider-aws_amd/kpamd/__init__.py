@@ -8,6 +8,8 @@ The surfaces mirror the reference's plugin/operator interface for the path:
   ClusterPlan(...).drift(subsets)             <- upstream disruption Drift: SimulateScheduling, the whole Solve
   ClusterPlan(...).command(subsets)           <- computeConsolidation's Command: the replacement NodeClaim + placements
   ClusterPlan(...).candidates(method, now)    <- upstream disruption GetCandidates: reasons, costs and the order
+  Context(...).scheduler_inputs(state)        <- upstream NewScheduler's inputs: daemonset overhead, remaining limits,
+                                                 StateNode.Available(), the nodes' remaining daemonset requests
 Everything computes behind the C ABI on the GPU; a missing libkp.so or HIP device raises.
 """
 import ctypes as C
@@ -141,6 +143,7 @@ def load_lib(path=None):
         "kp_cluster_simulate_explained": (C.c_int32, [C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32), C.c_uint32,
                                                       C.c_int32, P(C.c_uint32), C.c_uint32, P(abi.SimResult),
                                                       P(abi.SimWhy), P(C.c_uint64), P(C.c_uint64), P(abi.SolveStats)]),
+        "kp_scheduler_inputs": (C.c_int32, [C.c_void_p, P(abi.SchedState), P(abi.SchedOut), P(abi.SolveStats)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name, None)
@@ -180,6 +183,13 @@ class Context:
         ov = abi.Overrides(**kw)
         _check(self.lib, self.lib.kp_ctx_set_overrides(self.h, C.byref(ov)))
 
+    def scheduler_inputs(self, state):
+        """kp_scheduler_inputs: the daemonset overhead per NodePool template and per node, the remaining limits and the
+        nodes' available resources, computed on the device from a model.SchedulerState."""
+        arena = Arena()
+        st = abi.build_sched_state(arena, state)
+        return SchedulerInputs(*_scheduler_inputs_raw(self.lib, self.h, st))
+
     def close(self):
         if self.h:
             self.lib.kp_ctx_destroy(self.h)
@@ -190,6 +200,52 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+def _scheduler_inputs_raw(lib, ctx_h, st):
+    """One kp_scheduler_inputs call on a marshalled kp_sched_state: (node records, pool records, words, stats)."""
+    N, P, D = st.n_nodes, st.n_nodepools, st.n_daemonsets
+    W = max(1, (D + 63) // 64)
+    nodes = (abi.SchedNodeOut * max(1, N))()
+    pools = (abi.SchedPoolOut * max(1, P))()
+    words = np.zeros((max(1, N), W), dtype=np.uint64)
+    out = abi.SchedOut(nodes, pools, words.ctypes.data_as(C.POINTER(C.c_uint64)))
+    stats = abi.SolveStats()
+    _check(lib, lib.kp_scheduler_inputs(ctx_h, C.byref(st), C.byref(out), C.byref(stats)))
+    return nodes, pools, words[:N], N, P, stats
+
+
+class SchedulerInputs:
+    """What kp_scheduler_inputs returns. Per node: available, requests (the remaining daemonset requests),
+    n_compatible and the compatibility words (uint64 [N, ceil(D / 64)]: template d at bit d % 64 of word d // 64); per
+    NodePool: daemon_requests, remaining (None: the pool has no limits) and n_compatible."""
+
+    def __init__(self, nodes, pools, words, n_nodes, n_pools, stats=None):
+        self.raw_nodes, self.raw_pools = nodes, pools  # the records as the library wrote them (byte comparisons)
+        self.available = [abi.read_resources(nodes[i].available) for i in range(n_nodes)]
+        self.requests = [abi.read_resources(nodes[i].requests) for i in range(n_nodes)]
+        self.node_compatible = [int(nodes[i].n_compatible) for i in range(n_nodes)]
+        self.compat = words
+        self.daemon_requests = [abi.read_resources(pools[p].daemon_requests) for p in range(n_pools)]
+        self.remaining = [abi.read_resources(pools[p].remaining) if pools[p].remaining.present else None
+                          for p in range(n_pools)]
+        self.pool_compatible = [int(pools[p].n_compatible) for p in range(n_pools)]
+        self.stats = stats_dict(stats) if stats is not None else None
+
+    def apply(self, target):
+        """Write NodePool.daemon_requests, NodePool.limits (the remainder), ExistingNode.available and
+        ExistingNode.requests onto a model.Problem or model.Cluster whose NodePools and nodes are in the state's
+        order. Returns target."""
+        nodes = target.existing if hasattr(target, "existing") else [n.node for n in target.nodes]
+        if len(nodes) != len(self.available) or len(target.nodepools) != len(self.daemon_requests):
+            raise ValueError("the target's nodes and NodePools are not the state's")
+        for np_, dr, rem in zip(target.nodepools, self.daemon_requests, self.remaining):
+            np_.daemon_requests = dict(dr)
+            np_.limits = dict(rem) if rem is not None else {}
+        for n, av, rq in zip(nodes, self.available, self.requests):
+            n.available = dict(av)
+            n.requests = dict(rq)
+        return target
 
 
 class Catalog:

@@ -451,6 +451,71 @@ def build_drift_in(arena, inputs):
     return di
 
 
+class SchedPod(C.Structure):
+    _fields_ = [("requests", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class SchedNode(C.Structure):
+    _fields_ = [("labels", C.POINTER(Label)), ("taints", C.POINTER(Taint)), ("n_labels", C.c_uint32),
+                ("n_taints", C.c_uint32), ("allocatable", ResourceList), ("capacity", ResourceList)]
+
+
+class SchedState(C.Structure):
+    _fields_ = [("nodepools", C.POINTER(NodePool)), ("daemonsets", C.POINTER(PodShape)), ("nodes", C.POINTER(SchedNode)),
+                ("pod_offsets", C.POINTER(C.c_uint32)), ("pods", C.POINTER(SchedPod)),
+                ("request_rows", C.POINTER(ResourceList)), ("n_nodepools", C.c_uint32), ("n_daemonsets", C.c_uint32),
+                ("n_nodes", C.c_uint32), ("n_pods", C.c_uint32), ("n_request_rows", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class SchedNodeOut(C.Structure):
+    _fields_ = [("available", ResourceList), ("requests", ResourceList), ("n_compatible", C.c_uint32),
+                ("reserved_", C.c_uint32)]
+
+
+class SchedPoolOut(C.Structure):
+    _fields_ = [("daemon_requests", ResourceList), ("remaining", ResourceList), ("n_compatible", C.c_uint32),
+                ("reserved_", C.c_uint32)]
+
+
+class SchedOut(C.Structure):
+    _fields_ = [("nodes", C.POINTER(SchedNodeOut)), ("pools", C.POINTER(SchedPoolOut)), ("compat", C.POINTER(C.c_uint64))]
+
+
+SCHED_POD_DAEMON = 1
+
+
+def build_sched_state(arena, state):
+    """kpamd.model.SchedulerState -> kp_sched_state (buffers kept by the arena): the pods' request lists are interned
+    into the table of distinct rows, the pods laid out as the CSR."""
+    import numpy as np
+    nps = arena.arr(NodePool, [arena.nodepool(p, p.catalog) for p in state.nodepools])
+    dss = arena.arr(PodShape, [arena.shape(d) for d in state.daemonsets])
+    rows, row_of, nodes = [], {}, []
+    offs = np.zeros(len(state.nodes) + 1, dtype=np.uint32)
+    flat = []
+    for i, n in enumerate(state.nodes):
+        labels, nl = arena.labels(n.labels)
+        taints, nt = arena.taints(n.taints)
+        nodes.append(SchedNode(labels, taints, nl, nt, arena.resources(n.allocatable), arena.resources(n.capacity)))
+        for requests, is_daemon in n.pods:
+            key = tuple(sorted(requests.items()))
+            r = row_of.get(key)
+            if r is None:
+                r = row_of[key] = len(rows)
+                rows.append(arena.resources(requests))
+            flat.append((r, SCHED_POD_DAEMON if is_daemon else 0))
+        offs[i + 1] = len(flat)
+    pods = np.zeros(max(1, len(flat)), dtype=[("requests", "<u4"), ("flags", "<u4")])
+    if flat:
+        pods[:len(flat)] = flat
+    arena.keep.extend([offs, pods])
+    st = SchedState(nps, dss, arena.arr(SchedNode, nodes), offs.ctypes.data_as(C.POINTER(C.c_uint32)),
+                    pods.ctypes.data_as(C.POINTER(SchedPod)), arena.arr(ResourceList, rows), len(state.nodepools),
+                    len(state.daemonsets), len(state.nodes), len(flat), len(rows), 0)
+    arena.keep.append(st)
+    return st
+
+
 # enum kp_validity
 (VALID, INVALID_UNSCHEDULED, INVALID_NO_REPLACEMENT_NEEDED, INVALID_MULTIPLE, INVALID_NEEDS_REPLACEMENT,
  INVALID_NOT_SUBSET, INVALID_BUDGET) = range(7)

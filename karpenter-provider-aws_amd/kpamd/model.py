@@ -248,6 +248,28 @@ class DriftInputs:
 
 
 @dataclass
+class SchedNode:
+    """A node as kp_scheduler_inputs reads it: labels and taints as an ExistingNode carries them, status.allocatable
+    and status.capacity, and the pods bound to it as (requests, a DaemonSet owns it)."""
+    name: str
+    labels: Dict[str, str]
+    taints: List[Tuple[str, str, str]] = field(default_factory=list)
+    allocatable: Dict[str, int] = field(default_factory=dict)
+    capacity: Dict[str, int] = field(default_factory=dict)
+    pods: List[Tuple[Dict[str, int], bool]] = field(default_factory=list)
+
+
+@dataclass
+class SchedulerState:
+    """The inputs of kp_scheduler_inputs: the NodePools with spec.limits in `limits` (daemon_requests is ignored), the
+    DaemonSets' pod templates, and the nodes (in the order of Problem.existing / Cluster.nodes where the result is
+    applied to one)."""
+    nodepools: List[NodePool]
+    daemonsets: List["PodShape"]
+    nodes: List[SchedNode]
+
+
+@dataclass
 class Cluster:
     catalogs: List[List[InstanceType]]
     nodepools: List[NodePool]

@@ -948,3 +948,73 @@ def add_drift_inputs(cluster, seed, n_nodeclasses=4, n_amis=8, errors=True):
         nodes.append(d)
     cluster.drift_inputs = DriftInputs(classes, pools, nodes)
     return cluster.drift_inputs
+
+
+def add_scheduler_state(target, seed, n_daemonsets=8, taint_share=0.25):
+    """A randomized model.SchedulerState (kp_scheduler_inputs) derived from a synthetic Problem or Cluster, its nodes
+    in the target's order. A taint_share of the target's nodes is tainted first (dedicated=infra:NoSchedule or
+    soft:PreferNoSchedule; the state's nodes carry the same taints) and three quarters of the state's nodes get a
+    `team` label. The NodePools are the target's with spec.limits drawn per pool: cpu only, none, cpu and memory. The
+    daemonsets cycle through six forms (plain, a zone selector, two required terms of which the node side reads the
+    first, NotIn spot, Gt on instance-cpu, a team selector) and three toleration sets (none, Exists, dedicated=infra).
+    A node's allocatable and capacity are its instance type's (Cluster) or available plus the bound pods (Problem);
+    its bound pods are the target's plus a daemonset-owned pod for about half of the daemonsets, on a tenth of the
+    nodes with four times the requests so that the clamp bites, and on one node in twenty a pod as large as the node
+    so that available goes negative."""
+    from .model import SchedNode, SchedulerState
+    import copy
+    rng = np.random.default_rng(seed)
+    is_cluster = not hasattr(target, "existing")
+    base = [n.node for n in target.nodes] if is_cluster else list(target.existing)
+    zone, ct = "topology.kubernetes.io/zone", "karpenter.sh/capacity-type"
+    dss = []
+    for d in range(n_daemonsets):
+        sh = PodShape(req_res(int(rng.choice([20, 50, 100, 250])), int(rng.choice([32, 64, 128]))))
+        form = d % 6
+        if form == 1:
+            sh.node_selector = {zone: ZONES[int(rng.integers(0, len(ZONES)))]}
+        elif form == 2:
+            sh.required_terms = [[(zone, "In", [ZONES[int(rng.integers(0, len(ZONES)))]])], [(ct, "In", ["spot", "on-demand"])]]
+        elif form == 3:
+            sh.required_terms = [[(ct, "NotIn", ["spot"])]]
+        elif form == 4:
+            sh.required_terms = [[(K + "instance-cpu", "Gt", [str(int(rng.choice([2, 4, 8])))])]]
+        elif form == 5:
+            sh.node_selector = {"team": f"t{int(rng.integers(0, 2))}"}
+        if d % 11 == 10:
+            sh.preferred_terms = [(5, [(zone, "In", ["nowhere"])])]
+        sh.tolerations = [[], [("", "Exists", "", "")], [("dedicated", "Equal", "infra", "NoSchedule")]][(d // 2) % 3]
+        dss.append(sh)
+    pools = copy.deepcopy(target.nodepools)
+    n_nodes = max(1, len(base))
+    for p, np_ in enumerate(pools):
+        np_.daemon_requests = {}
+        np_.limits = [{"cpu": 6000 * n_nodes}, {}, {"cpu": 9000 * n_nodes, "memory": 16 * 1024 * MI * 1000 * n_nodes}][p % 3]
+    nodes = []
+    for i, n in enumerate(base):
+        r = rng.random(6)
+        if r[0] < taint_share:
+            n.taints = list(n.taints) + [("dedicated", "infra", "NoSchedule") if r[1] < 0.6 else ("soft", "", "PreferNoSchedule")]
+        labels = dict(n.labels)
+        if r[2] < 0.75:
+            labels["team"] = f"t{int(rng.integers(0, 3))}"
+        if is_cluster:
+            cn = target.nodes[i]
+            it = target.catalogs[cn.catalog][cn.instance_type]
+            alloc, cap = it.allocatable(), dict(it.capacity)
+            pods = [(target.shapes[int(target.pod_shape[p])].requests, False) for p in cn.pods]
+        else:
+            pods = [(req_res(int(rng.choice(CPU_GRID)), int(rng.choice(MEM_GRID))), False)
+                    for _ in range(int(rng.integers(0, 6)))]
+            alloc = dict(n.available)
+            for q, _ in pods:
+                for k, v in q.items():
+                    alloc[k] = alloc.get(k, 0) + v
+            cap = {k: v + v // 16 for k, v in alloc.items()}
+        scale = 4 if r[3] < 0.1 else 1
+        for d in np.flatnonzero(rng.random(n_daemonsets) < 0.5):
+            pods.append(({k: v * scale for k, v in dss[int(d)].requests.items()}, True))
+        if r[4] < 0.05:
+            pods.append(({"cpu": alloc.get("cpu", 0) + 1000, "pods": 1000}, False))
+        nodes.append(SchedNode(n.name, labels, list(n.taints), alloc, cap, pods))
+    return SchedulerState(pools, dss, nodes)
