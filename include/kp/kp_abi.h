@@ -10,6 +10,8 @@
  *                              R:pkg/providers/instancetype/offering/offering.go:68-98), resident on device
  *                             until its seqnum changes (R:instancetype.go:225-237 cacheKey).
  *   kp_instance_type_resolve <- instancetype.NewInstanceType (R:pkg/providers/instancetype/types.go:123-155)
+ *   kp_catalog_compile     <- the capacity / overhead and offering halves of that result for every EC2NodeClass in one
+ *                             call (NewInstanceType + createOfferings per (NodeClass, type) pair, on the device)
  *   kp_filter_compatible_available <- filter.CompatibleAvailableFilter
  *                             (R:pkg/providers/instance/filter/filter.go:39-64), batched: many
  *                             (requirements, requests) rows × one catalogue on the GPU.
@@ -1528,6 +1530,106 @@ typedef struct kp_sched_out {         /* caller-allocated */
   uint64_t* compat;                   /* n_nodes * max(1, ceil(n_daemonsets / 64)) words, or NULL */
 } kp_sched_out;
 int32_t kp_scheduler_inputs(kp_ctx* ctx, const kp_sched_state* state, kp_sched_out* out, kp_solve_stats* stats);
+
+/* ---- catalogue compile (additive, ABI v13) ---------------------------------------------------------------------
+ * kp_catalog_compile <- the resource half and the offering half of CloudProvider.GetInstanceTypes for EVERY
+ * EC2NodeClass in one call (instancetype.DefaultProvider.List, R:pkg/providers/instancetype/instancetype.go:129-171:
+ * NewInstanceType per (NodeClass, type), R:types.go:123-155; UpdateInstanceTypeCapacityFromNode's discovered memory,
+ * R:instancetype.go:213-215,330-355; offering.InjectOfferings -> createOfferings, R:offering/offering.go:101-187).
+ * The label half (computeRequirements) stays with the caller, as for kp_instance_type_resolve; the caller assembles
+ * kp_instance_type lists for kp_catalog_upload from these tables.
+ *
+ * Inputs. types and nodeclasses are kp_ec2_info / kp_nodeclass as kp_instance_type_resolve takes them, opts likewise.
+ * all_zones is the provider's allZones (at most 64, distinct); type_zones[t] has bit z set when type t is offered in
+ * all_zones[z] (instanceTypesOfferings). od_price[t] and spot_price[t * n_all_zones + z] are what OnDemandPrice(type)
+ * and SpotPrice(type, zone) return (R:pkg/providers/pricing/pricing.go:145-170: the caller resolves spot's default
+ * price before spotPricingUpdated): NaN = no price (hasPrice false, price 0.0), else kp_offering.price's domain.
+ * unavailable lists the UnavailableOfferings entries (R:pkg/cache/unavailableofferings.go:58-63); an entry names
+ *   a (capacity type, type, zone) triple:  capacity_type and zone set, type >= 0
+ *   a capacity type alone:                 capacity_type set, zone NULL, type < 0
+ *   a zone alone:                          zone set, capacity_type NULL, type < 0
+ * with capacity types "on-demand" and "spot". Capacity reservations are per NodeClass: reservation_offsets
+ * (n_nodeclasses + 1 entries) is the CSR of nodeclass -> reservations. reserved_capacity is the ReservedCapacity
+ * feature gate: with it 0, or with no reservation listed, there are no reserved offerings (the list is still
+ * validated, out->reserved is not written). discovered_memory[n * n_types + t] (may be NULL) is the memory capacity in
+ * bytes a real node of that pair reported; negative: none.
+ *
+ * Outputs, pair index i = n * n_types + t. Each array may be NULL to skip it; all NULL is KP_E_INVAL.
+ *   capacity[i], overhead[i]  exactly kp_instance_type_resolve(opts, &types[t], &nodeclasses[n]), present masks
+ *                             included, except that a discovered memory replaces capacity.milli[KP_RES_MEMORY] alone
+ *                             (bytes * 1000); the overhead is still computed from memory()
+ *   kube_reserved[i], system_reserved[i], eviction_threshold[i]  exactly kp_instance_type_overhead's lists
+ *   it_zones[i]   type_zones[t] AND {z : all_zones[z] is a subnet zone of nodeclass n}: the values of the type's zone
+ *                 requirement. A subnet zone that is not in all_zones takes no part.
+ *   price[(t * n_all_zones + z) * 2 + c]   capacity type c: 0 on-demand, 1 spot (KP_CT_*); 0.0 without a price.
+ *                 It does not depend on the NodeClass.
+ *   available[i * 2 + c]   bit z = !IsUnavailable(type, zone, capacity type) AND hasPrice AND z in it_zones
+ *                 (R:offering.go:121-141). An offering in a zone outside the NodeClass's subnets exists (createOfferings
+ *                 iterates allZones), is never available and carries no zone id.
+ *   reserved[r]   one record per input reservation, in input order: price = od / 10,000,000.0 (0.0 without an
+ *                 on-demand price), available = count != 0 AND zone in it_zones of its (NodeClass, type),
+ *                 capacity = the count (R:offering.go:155-185)
+ *
+ * ctx == NULL validates on the host and writes nothing. Errors: KP_E_INVAL for a NULL in / out, all outputs NULL, a
+ * NULL array whose count is not 0 (types, nodeclasses, all_zones, type_zones, od_price, spot_price, unavailable,
+ * reservations with reservation_offsets; a nodeclass's zones or block_device_mappings), a NULL or repeated zone name,
+ * a type_zones bit at or past n_all_zones, a negative price, a discovered memory above INT64_MAX / 1000 bytes, an
+ * unavailable entry of none of the three forms or naming an unknown capacity type, a zone not in all_zones or a type out of range, reservation_offsets that do not start at
+ * 0, decrease, or end elsewhere than n_reservations, a reservation with a NULL id, a type out of range or a zone not
+ * in all_zones. KP_E_UNSUPPORTED for more than 64 zones and for n_nodeclasses * n_types or n_types * n_all_zones * 2
+ * of 2^31 or more (checked before any array is read). stats: device_ms (the kernels), host_ms (the call), prepare_ms
+ * (the host compile, part of host_ms). */
+#define KP_CT_ON_DEMAND 0
+#define KP_CT_SPOT 1
+typedef struct kp_unavailable {
+  const char* capacity_type;          /* "on-demand" | "spot"; NULL: the entry names a zone alone */
+  const char* zone;                   /* NULL: the entry names a capacity type alone */
+  int32_t type;                       /* index into types; < 0: none */
+  int32_t reserved_;
+} kp_unavailable;
+typedef struct kp_compile_reservation { /* EC2NodeClass.status.capacityReservations entry + its available count */
+  const char* id;
+  const char* zone;                   /* availabilityZone */
+  const char* reservation_type;       /* "default" | "capacity-block": not read, it belongs to the label half */
+  uint32_t type;                      /* index into types (the reservation's instanceType) */
+  int32_t available_count;            /* capacityReservationProvider.GetAvailableInstanceCount(id) */
+} kp_compile_reservation;
+typedef struct kp_reserved_offering {
+  double price;
+  int32_t available;
+  int32_t capacity;                   /* -> kp_offering.reservation_capacity */
+} kp_reserved_offering;
+typedef struct kp_compile_in {
+  kp_options opts;
+  const kp_ec2_info* types;
+  const kp_nodeclass* nodeclasses;
+  const char* const* all_zones;
+  const uint64_t* type_zones;         /* n_types */
+  const double* od_price;             /* n_types */
+  const double* spot_price;           /* n_types * n_all_zones */
+  const kp_unavailable* unavailable;
+  const uint32_t* reservation_offsets; /* n_nodeclasses + 1, or NULL with n_reservations 0 */
+  const kp_compile_reservation* reservations;
+  const int64_t* discovered_memory;   /* n_nodeclasses * n_types, or NULL */
+  uint32_t n_types;
+  uint32_t n_nodeclasses;
+  uint32_t n_all_zones;
+  uint32_t n_unavailable;
+  uint32_t n_reservations;
+  int32_t reserved_capacity;          /* the ReservedCapacity feature gate */
+} kp_compile_in;
+typedef struct kp_compile_out {       /* caller-allocated; any may be NULL */
+  kp_resource_list* capacity;         /* n_nodeclasses * n_types */
+  kp_resource_list* overhead;
+  kp_resource_list* kube_reserved;
+  kp_resource_list* system_reserved;
+  kp_resource_list* eviction_threshold;
+  uint64_t* it_zones;                 /* n_nodeclasses * n_types */
+  double* price;                      /* n_types * n_all_zones * 2 */
+  uint64_t* available;                /* n_nodeclasses * n_types * 2 */
+  kp_reserved_offering* reserved;     /* n_reservations */
+} kp_compile_out;
+int32_t kp_catalog_compile(kp_ctx* ctx, const kp_compile_in* in, const kp_compile_out* out, kp_solve_stats* stats);
 
 /* The reduction kp_consolidate_argmin applies to the gathered per-rank records (host-only; exposed for callers that
  * reduce over another transport, and for tests): counts are summed, the best record wins. */

@@ -32,6 +32,7 @@
 
 #include "kp/kp_abi.h"
 #include "kp_cand.h"
+#include "kp_catcomp.h"
 #include "kp_driftdet.h"
 #include "kp_schedin.h"
 #include "kp_device.h"
@@ -230,6 +231,9 @@ struct kp_ctx {
   // kp_scheduler_inputs' device arena, kept across calls (grown, never shrunk)
   void* schedin = nullptr;
   size_t schedin_bytes = 0;
+  // kp_catalog_compile's, likewise
+  void* catcomp = nullptr;
+  size_t catcomp_bytes = 0;
   // kp_ctx_destroy's reference plus one per live dependent (catalogue, plan, communicator): the context is freed
   // when the last goes, so a dependent may be destroyed after the context (any order, e.g. a garbage collector's)
   std::atomic<int> refs{1};
@@ -239,6 +243,7 @@ static void CtxFree(kp_ctx* c) {
   c->bases.clear();
   if (c->spare) (void)hipFree(c->spare);
   if (c->schedin) (void)hipFree(c->schedin);
+  if (c->catcomp) (void)hipFree(c->catcomp);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->ev2) (void)hipEventDestroy(c->ev2);
@@ -9126,6 +9131,235 @@ int32_t kp_scheduler_inputs(kp_ctx* ctx, const kp_sched_state* st, kp_sched_out*
   if (N) HIPCHK(hipMemcpyAsync(out->nodes, a.node_out, sizeof(SiNodeOut) * N, hipMemcpyDeviceToHost, s));
   if (P) HIPCHK(hipMemcpyAsync(out->pools, a.pool_out, sizeof(SiPoolOut) * P, hipMemcpyDeviceToHost, s));
   if (N && out->compat) HIPCHK(hipMemcpyAsync(out->compat, a.compat, sizeof(uint64_t) * (size_t)N * W, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (stats) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    stats->device_ms = ms;
+    stats->prepare_ms = compile_ms;
+    stats->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return KP_OK;
+}
+
+}  // extern "C"
+
+// ---- The catalogue compile (kp_catalog_compile) ---------------------------------------------------------------------
+// The host does strings only: a type's architecture and GPU manufacturer become flags, zone names indices into
+// all_zones, the unavailable offerings one bit row over the types per (capacity type, zone) plus the two wide masks,
+// and every NodeClass one fixed-width record (CcNodeClass). Every number of the result is the device's
+// (kp_catcomp.hip); kp_instance_type_resolve and kp_instance_type_overhead above are what the tests hold it to.
+static_assert(sizeof(kp_reserved_offering) == 16, "the reserved record is written by the device as it stands");
+
+namespace {
+int CapacityTypeIndex(const char* ct) {
+  if (ct && strcmp(ct, "on-demand") == 0) return KP_CT_ON_DEMAND;
+  if (ct && strcmp(ct, "spot") == 0) return KP_CT_SPOT;
+  return -1;
+}
+// Validation and the zone dictionary (zone name -> index into all_zones)
+int32_t CatCompValidate(const kp_compile_in* in, const kp_compile_out* out, std::unordered_map<string, uint32_t>& zone_id) {
+  if (!in || !out) return fail(KP_E_INVAL, "null in or out");
+  if (!out->capacity && !out->overhead && !out->kube_reserved && !out->system_reserved && !out->eviction_threshold &&
+      !out->it_zones && !out->price && !out->available && !out->reserved)
+    return fail(KP_E_INVAL, "every output is NULL");
+  const uint32_t T = in->n_types, N = in->n_nodeclasses, Z = in->n_all_zones;
+  // the caps first: nothing is read before them
+  if (Z > 64) return fail(KP_E_UNSUPPORTED, "%u zones (max 64)", Z);
+  if ((uint64_t)N * T >= (1ull << 31)) return fail(KP_E_UNSUPPORTED, "%u NodeClasses x %u types (max 2^31 - 1 pairs)", N, T);
+  if ((uint64_t)T * Z * 2 >= (1ull << 31)) return fail(KP_E_UNSUPPORTED, "%u types x %u zones (max 2^30 - 1 prices)", T, Z);
+  if (N > 65535) return fail(KP_E_UNSUPPORTED, "%u NodeClasses (max 65535)", N);
+  if ((T && !in->types) || (N && !in->nodeclasses) || (Z && !in->all_zones) || (T && !in->type_zones) ||
+      (T && !in->od_price) || (T && Z && !in->spot_price) || (in->n_unavailable && !in->unavailable) ||
+      (in->n_reservations && (!in->reservations || !in->reservation_offsets)))
+    return fail(KP_E_INVAL, "null types, nodeclasses, all_zones, type_zones, od_price, spot_price, unavailable, "
+                            "reservations or reservation_offsets");
+  for (uint32_t z = 0; z < Z; z++) {
+    if (!in->all_zones[z]) return fail(KP_E_INVAL, "all_zones[%u] is NULL", z);
+    if (!zone_id.emplace(in->all_zones[z], z).second) return fail(KP_E_INVAL, "all_zones[%u] (%s) repeats", z, in->all_zones[z]);
+  }
+  const uint64_t zone_bits = Z == 64 ? ~0ull : (1ull << Z) - 1;
+  for (uint32_t t = 0; t < T; t++) {
+    if (in->type_zones[t] & ~zone_bits) return fail(KP_E_INVAL, "type %u: type_zones names a zone past n_all_zones = %u", t, Z);
+    if (in->od_price[t] < 0) return fail(KP_E_INVAL, "type %u: on-demand price %g (a price is a number >= 0)", t, in->od_price[t]);
+    for (uint32_t z = 0; z < Z; z++)
+      if (in->spot_price[(size_t)t * Z + z] < 0)
+        return fail(KP_E_INVAL, "type %u, zone %u: spot price %g (a price is a number >= 0)", t, z, in->spot_price[(size_t)t * Z + z]);
+  }
+  for (uint32_t n = 0; n < N; n++) {
+    const kp_nodeclass& nc = in->nodeclasses[n];
+    if (nc.n_zones && !nc.zones) return fail(KP_E_INVAL, "NodeClass %u: null zones", n);
+    for (uint32_t j = 0; j < nc.n_zones; j++)
+      if (!nc.zones[j]) return fail(KP_E_INVAL, "NodeClass %u: zone %u is NULL", n, j);
+    if (nc.n_block_device_mappings && !nc.block_device_mappings) return fail(KP_E_INVAL, "NodeClass %u: null block_device_mappings", n);
+  }
+  if (in->discovered_memory)  // bytes become milli-units on the device
+    for (size_t i = 0; i < (size_t)N * T; i++)
+      if (in->discovered_memory[i] > std::numeric_limits<int64_t>::max() / 1000)
+        return fail(KP_E_INVAL, "discovered_memory[%zu] = %lld bytes does not fit milli-units", i, (long long)in->discovered_memory[i]);
+  for (uint32_t i = 0; i < in->n_unavailable; i++) {
+    const kp_unavailable& u = in->unavailable[i];
+    const bool triple = u.capacity_type && u.zone && u.type >= 0, ct_alone = u.capacity_type && !u.zone && u.type < 0,
+               zone_alone = !u.capacity_type && u.zone && u.type < 0;
+    if (!triple && !ct_alone && !zone_alone)
+      return fail(KP_E_INVAL, "unavailable %u: not a (capacity type, type, zone) triple, a capacity type alone or a zone alone", i);
+    if (u.capacity_type && CapacityTypeIndex(u.capacity_type) < 0)
+      return fail(KP_E_INVAL, "unavailable %u: unknown capacity type %s", i, u.capacity_type);
+    if (u.zone && !zone_id.count(u.zone)) return fail(KP_E_INVAL, "unavailable %u: zone %s is not in all_zones", i, u.zone);
+    if (triple && (uint32_t)u.type >= T) return fail(KP_E_INVAL, "unavailable %u: type %d of %u", i, u.type, T);
+  }
+  if (in->n_reservations) {
+    const uint32_t* off = in->reservation_offsets;
+    if (off[0] != 0) return fail(KP_E_INVAL, "reservation_offsets[0] = %u", off[0]);
+    for (uint32_t n = 0; n < N; n++)
+      if (off[n + 1] < off[n]) return fail(KP_E_INVAL, "reservation_offsets decrease at NodeClass %u", n);
+    if (off[N] != in->n_reservations)
+      return fail(KP_E_INVAL, "reservation_offsets end at %u, n_reservations = %u", off[N], in->n_reservations);
+    for (uint32_t r = 0; r < in->n_reservations; r++) {
+      const kp_compile_reservation& cr = in->reservations[r];
+      if (!cr.id) return fail(KP_E_INVAL, "reservation %u: null id", r);
+      if (cr.type >= T) return fail(KP_E_INVAL, "reservation %u (%s): type %u of %u", r, cr.id, cr.type, T);
+      if (!cr.zone || !zone_id.count(cr.zone))
+        return fail(KP_E_INVAL, "reservation %u (%s): zone %s is not in all_zones", r, cr.id, cr.zone ? cr.zone : "(null)");
+    }
+  }
+  return KP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t kp_catalog_compile(kp_ctx* ctx, const kp_compile_in* in, const kp_compile_out* out, kp_solve_stats* stats) {
+  std::unordered_map<string, uint32_t> zone_id;
+  if (int32_t rc = CatCompValidate(in, out, zone_id)) return rc;
+  if (!ctx) return KP_OK;  // host-only validation
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  HIPCHK(hipSetDevice(ctx->device));
+  if (stats) memset(stats, 0, sizeof *stats);
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint32_t T = in->n_types, N = in->n_nodeclasses, Z = in->n_all_zones;
+  const uint32_t R = in->reserved_capacity ? in->n_reservations : 0;  // the ReservedCapacity feature gate
+  const uint32_t W = std::max<uint32_t>(1, (T + 63) / 64);
+  // the types as a structure of arrays
+  const size_t T1 = std::max<uint32_t>(T, 1);
+  vector<int32_t> vcpu(T1), gpu_count(T1), neuron_devices(T1), neuron_cores(T1), efa(T1), max_enis(T1), ipv4(T1), branch(T1);
+  vector<int64_t> memory_mib(T1), storage_gb(T1);
+  vector<uint32_t> type_flags(T1, 0);
+  for (uint32_t t = 0; t < T; t++) {
+    const kp_ec2_info& e = in->types[t];
+    vcpu[t] = e.vcpu, memory_mib[t] = e.memory_mib, gpu_count[t] = e.gpu_count, neuron_devices[t] = e.neuron_devices;
+    neuron_cores[t] = e.neuron_cores_per_device, efa[t] = e.efa, max_enis[t] = e.max_enis, ipv4[t] = e.ipv4_per_eni;
+    branch[t] = e.branch_enis;
+    storage_gb[t] = e.instance_storage_gb > 0 ? e.instance_storage_gb : e.local_nvme_gb;
+    const char* gm = e.gpu_manufacturer ? e.gpu_manufacturer : "";
+    const uint32_t gpu = strcmp(gm, "nvidia") == 0 ? CC_GPU_NVIDIA : strcmp(gm, "amd") == 0 ? CC_GPU_AMD
+                         : strcmp(gm, "habana") == 0 ? CC_GPU_HABANA : CC_GPU_NONE;
+    type_flags[t] = (e.arch && strcmp(e.arch, "arm64") == 0 ? CC_T_ARM64 : 0) | (e.arch && strcmp(e.arch, "amd64") == 0 ? CC_T_AMD64 : 0) |
+                    (e.in_limits_table ? CC_T_IN_LIMITS : 0) | (e.trunking ? CC_T_TRUNKING : 0) | (gpu << CC_T_GPU_SHIFT);
+  }
+  // every NodeClass as one record
+  vector<CcNodeClass> ncs(std::max<uint32_t>(N, 1));
+  memset(ncs.data(), 0, ncs.size() * sizeof(CcNodeClass));
+  const kp_ec2_info no_store{};
+  for (uint32_t n = 0; n < N; n++) {
+    const kp_nodeclass& nc = in->nodeclasses[n];
+    CcNodeClass& c = ncs[n];
+    const FamilyFlags fam = Family(&nc);
+    c.flags = (fam.eni_memory ? CC_N_ENI_MEMORY : 0) | (fam.pods_per_core ? CC_N_PODS_PER_CORE : 0) |
+              (fam.eni_density ? CC_N_ENI_DENSITY : 0) | (fam.windows ? CC_N_WINDOWS : 0) |
+              (nc.instance_store_policy == KP_INSTANCE_STORE_RAID0 ? CC_N_RAID0 : 0);
+    if (const kp_kubelet* kl = nc.kubelet) {
+      c.flags |= CC_N_KUBELET | (kl->has_eviction_hard ? CC_N_EVICTION_HARD : 0) |
+                 (kl->has_eviction_soft && fam.eviction_soft ? CC_N_EVICTION_SOFT : 0);
+      c.kube_reserved = kl->kube_reserved, c.system_reserved = kl->system_reserved;
+      c.hard_memory = kl->hard_memory_available, c.hard_nodefs = kl->hard_nodefs_available;
+      c.soft_memory = kl->soft_memory_available, c.soft_nodefs = kl->soft_nodefs_available;
+    }
+    kp_nodeclass no_raid = nc;  // what EphemeralBytes returns without RAID0: the type plays no part in it
+    no_raid.instance_store_policy = KP_INSTANCE_STORE_NONE;
+    c.storage_bytes = EphemeralBytes(&no_store, &no_raid);
+    c.max_pods = nc.max_pods, c.pods_per_core = nc.pods_per_core;
+    for (uint32_t j = 0; j < nc.n_zones; j++) {
+      auto f = zone_id.find(nc.zones[j]);
+      if (f != zone_id.end()) c.zone_mask |= 1ull << f->second;
+    }
+  }
+  // the unavailable offerings
+  vector<uint64_t> ice_rows((size_t)2 * std::max<uint32_t>(Z, 1) * W, 0);
+  uint64_t ice_zones = 0;
+  uint32_t ice_cts = 0;
+  for (uint32_t i = 0; i < in->n_unavailable; i++) {
+    const kp_unavailable& u = in->unavailable[i];
+    if (u.capacity_type && u.zone)
+      ice_rows[((size_t)CapacityTypeIndex(u.capacity_type) * Z + zone_id[u.zone]) * W + ((uint32_t)u.type >> 6)] |= 1ull << (u.type & 63);
+    else if (u.capacity_type)
+      ice_cts |= 1u << CapacityTypeIndex(u.capacity_type);
+    else
+      ice_zones |= 1ull << zone_id[u.zone];
+  }
+  vector<CcReservation> res(std::max<uint32_t>(R, 1));
+  for (uint32_t n = 0; n < N && R; n++)
+    for (uint32_t r = in->reservation_offsets[n]; r < in->reservation_offsets[n + 1]; r++)
+      res[r] = CcReservation{n, in->reservations[r].type, zone_id[in->reservations[r].zone], in->reservations[r].available_count};
+  const size_t pairs = (size_t)N * T, P1 = std::max<size_t>(pairs, 1);
+  Blob blob;
+  const size_t o_vcpu = blob.put(vcpu), o_mem = blob.put(memory_mib), o_tf = blob.put(type_flags), o_gpu = blob.put(gpu_count),
+               o_nd = blob.put(neuron_devices), o_ncore = blob.put(neuron_cores), o_efa = blob.put(efa), o_enis = blob.put(max_enis),
+               o_ipv4 = blob.put(ipv4), o_branch = blob.put(branch), o_sgb = blob.put(storage_gb),
+               o_tz = blob.put(in->type_zones, T), o_od = blob.put(in->od_price, T), o_spot = blob.put(in->spot_price, (size_t)T * Z),
+               o_ncs = blob.put(ncs), o_ice = blob.put(ice_rows), o_res = blob.put(res),
+               o_disc = in->discovered_memory ? blob.put(in->discovered_memory, pairs) : 0;
+  const size_t o_lists = blob.reserve_dev(sizeof(kp_resource_list) * P1 * 5), o_itz = blob.reserve_dev(sizeof(uint64_t) * P1),
+               o_avail = blob.reserve_dev(sizeof(uint64_t) * P1 * 2),
+               o_price = blob.reserve_dev(sizeof(double) * std::max<size_t>((size_t)T * Z * 2, 1)),
+               o_rout = blob.reserve_dev(sizeof(kp_reserved_offering) * std::max<uint32_t>(R, 1));
+  if (blob.total() > ctx->catcomp_bytes) {
+    if (ctx->catcomp) (void)hipFree(ctx->catcomp);
+    ctx->catcomp = nullptr, ctx->catcomp_bytes = 0;
+    HIPCHK(hipMalloc(&ctx->catcomp, blob.total()));
+    ctx->catcomp_bytes = blob.total();
+  }
+  uint8_t* base = (uint8_t*)ctx->catcomp;
+  CatCompArgs a{};
+  a.n_types = (int)T, a.n_nodeclasses = (int)N, a.n_zones = (int)Z, a.n_reservations = (int)R, a.words = (int)W;
+  a.vm_memory_overhead_percent = in->opts.vm_memory_overhead_percent, a.reserved_enis = in->opts.reserved_enis;
+  a.vcpu = (const int32_t*)(base + o_vcpu), a.memory_mib = (const int64_t*)(base + o_mem);
+  a.type_flags = (const uint32_t*)(base + o_tf), a.gpu_count = (const int32_t*)(base + o_gpu);
+  a.neuron_devices = (const int32_t*)(base + o_nd), a.neuron_cores = (const int32_t*)(base + o_ncore);
+  a.efa = (const int32_t*)(base + o_efa), a.max_enis = (const int32_t*)(base + o_enis);
+  a.ipv4_per_eni = (const int32_t*)(base + o_ipv4), a.branch_enis = (const int32_t*)(base + o_branch);
+  a.storage_gb = (const int64_t*)(base + o_sgb), a.type_zones = (const uint64_t*)(base + o_tz);
+  a.od_price = (const double*)(base + o_od), a.spot_price = (const double*)(base + o_spot);
+  a.nodeclasses = (const CcNodeClass*)(base + o_ncs);
+  a.discovered = in->discovered_memory ? (const int64_t*)(base + o_disc) : nullptr;
+  a.ice_rows = (const uint64_t*)(base + o_ice), a.ice_zones = ice_zones, a.ice_capacity_types = ice_cts;
+  a.reservations = (const CcReservation*)(base + o_res);
+  kp_resource_list* lists = (kp_resource_list*)(base + o_lists);
+  a.capacity = lists, a.overhead = lists + P1, a.kube_reserved = lists + 2 * P1, a.system_reserved = lists + 3 * P1;
+  a.eviction_threshold = lists + 4 * P1;
+  a.it_zones = (uint64_t*)(base + o_itz), a.available = (uint64_t*)(base + o_avail), a.price = (double*)(base + o_price);
+  a.reserved = (kp_reserved_offering*)(base + o_rout);
+  const double compile_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  hipStream_t s = ctx->stream;
+  HIPCHK(hipMemcpyAsync(base, blob.host.data(), blob.host.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(hipEventRecord(ctx->ev0, s));
+  HIPCHK(launch_catalog_compile(a, s));
+  HIPCHK(hipEventRecord(ctx->ev1, s));
+  const struct {
+    void* dst;
+    const void* src;
+    size_t bytes;
+  } back[] = {{out->capacity, a.capacity, sizeof(kp_resource_list) * pairs},
+              {out->overhead, a.overhead, sizeof(kp_resource_list) * pairs},
+              {out->kube_reserved, a.kube_reserved, sizeof(kp_resource_list) * pairs},
+              {out->system_reserved, a.system_reserved, sizeof(kp_resource_list) * pairs},
+              {out->eviction_threshold, a.eviction_threshold, sizeof(kp_resource_list) * pairs},
+              {out->it_zones, a.it_zones, sizeof(uint64_t) * pairs},
+              {out->available, a.available, sizeof(uint64_t) * pairs * 2},
+              {out->price, a.price, sizeof(double) * (size_t)T * Z * 2},
+              {out->reserved, a.reserved, sizeof(kp_reserved_offering) * R}};
+  for (auto& b : back)
+    if (b.dst && b.bytes) HIPCHK(hipMemcpyAsync(b.dst, b.src, b.bytes, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   if (stats) {
     float ms = 0;

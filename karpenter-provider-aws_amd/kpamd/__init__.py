@@ -10,6 +10,8 @@ The surfaces mirror the reference's plugin/operator interface for the path:
   ClusterPlan(...).candidates(method, now)    <- upstream disruption GetCandidates: reasons, costs and the order
   Context(...).scheduler_inputs(state)        <- upstream NewScheduler's inputs: daemonset overhead, remaining limits,
                                                  StateNode.Available(), the nodes' remaining daemonset requests
+  Context(...).compile_catalogs(rows, ncs)    <- GetInstanceTypes' resource and offering halves for every EC2NodeClass
+                                                 (catalog.build_catalogs assembles the InstanceType lists from them)
 Everything computes behind the C ABI on the GPU; a missing libkp.so or HIP device raises.
 """
 import ctypes as C
@@ -144,6 +146,7 @@ def load_lib(path=None):
                                                       C.c_int32, P(C.c_uint32), C.c_uint32, P(abi.SimResult),
                                                       P(abi.SimWhy), P(C.c_uint64), P(C.c_uint64), P(abi.SolveStats)]),
         "kp_scheduler_inputs": (C.c_int32, [C.c_void_p, P(abi.SchedState), P(abi.SchedOut), P(abi.SolveStats)]),
+        "kp_catalog_compile": (C.c_int32, [C.c_void_p, P(abi.CompileIn), P(abi.CompileOut), P(abi.SolveStats)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name, None)
@@ -190,6 +193,27 @@ class Context:
         st = abi.build_sched_state(arena, state)
         return SchedulerInputs(*_scheduler_inputs_raw(self.lib, self.h, st))
 
+    def compile_catalogs(self, rows, nodeclasses, all_zones=None, type_zones=None, spot_prices=None, unavailable=(),
+                         reservations=None, discovered_memory=None, reserved_capacity=True, outputs=None, opts=None):
+        """kp_catalog_compile: the capacity / overhead lists and the offering tables of every (NodeClass, instance
+        type) pair, computed on the device. rows: EC2 table rows; nodeclasses: one dict of
+        catalog.nodeclass keyword arguments per EC2NodeClass; all_zones: the provider's zones (default catalog.ZONES);
+        type_zones: per row, the zones it is offered in as bits over all_zones (default: all); spot_prices:
+        {(type name, zone): price}, a missing key is no price (default catalog.default_spot_prices); a row's od_price
+        < 0 is no on-demand price; unavailable: (capacity type, type name, zone) triples, capacity types and zones;
+        reservations: per NodeClass a list of catalog.CapacityReservation; discovered_memory: {(NodeClass index, type
+        name): bytes}; outputs: the tables wanted (default abi.COMPILE_OUTPUTS); opts: abi.Options in place of the
+        context's (the call carries its own kp_options). Returns a dict of numpy arrays:
+        the five lists [N, T] of abi.resource_list_dtype(), it_zones [N, T], price [T, Z, 2], available [N, T, 2],
+        reserved [n_reservations] of abi.reserved_offering_dtype(), plus "stats"."""
+        from . import catalog
+        all_zones = list(catalog.ZONES if all_zones is None else all_zones)
+        spot_prices = catalog.default_spot_prices(rows, all_zones) if spot_prices is None else spot_prices
+        arena = Arena()
+        cin = build_compile_in(arena, opts or self.opts, rows, nodeclasses, all_zones, type_zones, spot_prices, unavailable,
+                               reservations, discovered_memory, reserved_capacity)
+        return _catalog_compile_raw(self.lib, self.h, cin, abi.COMPILE_OUTPUTS if outputs is None else outputs)
+
     def close(self):
         if self.h:
             self.lib.kp_ctx_destroy(self.h)
@@ -200,6 +224,85 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+def build_compile_in(arena, opts, rows, nodeclasses, all_zones, type_zones=None, spot_prices=None, unavailable=(),
+                     reservations=None, discovered_memory=None, reserved_capacity=True):
+    """The arguments of Context.compile_catalogs -> kp_compile_in (buffers kept by the arena)."""
+    from . import catalog
+    T, N, Z = len(rows), len(nodeclasses), len(all_zones)
+    index = {r["name"]: t for t, r in enumerate(rows)}
+    nan = float("nan")
+    tz = np.full(max(1, T), (1 << Z) - 1 if type_zones is None else 0, dtype=np.uint64)
+    if type_zones is not None:
+        tz[:T] = np.asarray(list(type_zones), dtype=np.uint64)
+    od = np.full(max(1, T), nan)
+    spot = np.full((max(1, T), max(1, Z)), nan)
+    for t, r in enumerate(rows):
+        if r["od_price"] >= 0:
+            od[t] = r["od_price"]
+        for z, zone in enumerate(all_zones):
+            p = (spot_prices or {}).get((r["name"], zone))
+            if p is not None:
+                spot[t, z] = p
+    spot = np.ascontiguousarray(spot[:, :Z]) if Z else spot
+    unav = []
+    for u in unavailable:
+        if isinstance(u, tuple):
+            unav.append(abi.Unavailable(arena.s(u[0]), arena.s(u[2]), index[u[1]], 0))
+        elif u in abi.CAPACITY_TYPES:
+            unav.append(abi.Unavailable(arena.s(u), None, -1, 0))
+        else:
+            unav.append(abi.Unavailable(None, arena.s(u), -1, 0))
+    offs = np.zeros(N + 1, dtype=np.uint32)
+    res = []
+    for n, crs in enumerate(reservations or []):
+        for cr in crs:
+            res.append(abi.CompileReservation(arena.s(cr.id), arena.s(cr.availability_zone), arena.s(cr.reservation_type),
+                                              index[cr.instance_type], int(cr.available_count)))
+        offs[n + 1] = len(res)
+    offs[len(reservations or []) + 1:] = len(res)
+    disc = None
+    if discovered_memory is not None:
+        disc = np.full((max(1, N), max(1, T)), -1, dtype=np.int64)
+        for (n, name), b in discovered_memory.items():
+            disc[n, index[name]] = b
+    arena.keep.extend([tz, od, spot, offs, disc])
+    ptr = lambda a, ct: a.ctypes.data_as(C.POINTER(ct))
+    cin = abi.CompileIn(opts, arena.arr(abi.EC2Info, [catalog.ec2_info(arena, r) for r in rows]),
+                        arena.arr(abi.NodeClass, [catalog.nodeclass(arena, **kw) for kw in nodeclasses]),
+                        arena.arr(C.c_char_p, [arena.s(z) for z in all_zones]), ptr(tz, C.c_uint64), ptr(od, C.c_double),
+                        ptr(spot, C.c_double), arena.arr(abi.Unavailable, unav), ptr(offs, C.c_uint32),
+                        arena.arr(abi.CompileReservation, res), None if disc is None else ptr(disc, C.c_int64),
+                        T, N, Z, len(unav), len(res), 1 if reserved_capacity else 0)
+    arena.keep.append(cin)
+    return cin
+
+
+def _catalog_compile_raw(lib, ctx_h, cin, outputs=abi.COMPILE_OUTPUTS):
+    """One kp_catalog_compile call on a marshalled kp_compile_in: {output name: numpy array} of the outputs asked
+    for, plus "stats"."""
+    N, T, Z, R = cin.n_nodeclasses, cin.n_types, cin.n_all_zones, cin.n_reservations
+    rl = abi.resource_list_dtype()
+    shapes = {"it_zones": ((N, T), np.uint64), "price": ((T, Z, 2), np.float64), "available": ((N, T, 2), np.uint64),
+              "reserved": ((R,), abi.reserved_offering_dtype())}
+    shapes.update({k: ((N, T), rl) for k in abi.COMPILE_LISTS})
+    unknown = set(outputs) - set(abi.COMPILE_OUTPUTS)
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}")
+    tables, out = {}, abi.CompileOut()
+    for k, ctype in abi.CompileOut._fields_:
+        if k not in outputs:
+            continue
+        shape, dt = shapes[k]
+        n = int(np.prod(shape))
+        buf = np.zeros(max(1, n), dtype=dt)  # (never a NULL pointer for an output that was asked for)
+        tables[k] = buf[:n].reshape(shape)
+        setattr(out, k, C.cast(buf.ctypes.data, ctype))
+    stats = abi.SolveStats()
+    _check(lib, lib.kp_catalog_compile(ctx_h, C.byref(cin), C.byref(out), C.byref(stats)))
+    tables["stats"] = stats_dict(stats)
+    return tables
 
 
 def _scheduler_inputs_raw(lib, ctx_h, st):

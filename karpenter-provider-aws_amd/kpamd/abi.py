@@ -516,6 +516,53 @@ def build_sched_state(arena, state):
     return st
 
 
+class Unavailable(C.Structure):
+    _fields_ = [("capacity_type", C.c_char_p), ("zone", C.c_char_p), ("type", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class CompileReservation(C.Structure):
+    _fields_ = [("id", C.c_char_p), ("zone", C.c_char_p), ("reservation_type", C.c_char_p), ("type", C.c_uint32),
+                ("available_count", C.c_int32)]
+
+
+class ReservedOffering(C.Structure):
+    _fields_ = [("price", C.c_double), ("available", C.c_int32), ("capacity", C.c_int32)]
+
+
+class CompileIn(C.Structure):
+    _fields_ = [("opts", Options), ("types", C.POINTER(EC2Info)), ("nodeclasses", C.POINTER(NodeClass)),
+                ("all_zones", C.POINTER(C.c_char_p)), ("type_zones", C.POINTER(C.c_uint64)),
+                ("od_price", C.POINTER(C.c_double)), ("spot_price", C.POINTER(C.c_double)),
+                ("unavailable", C.POINTER(Unavailable)), ("reservation_offsets", C.POINTER(C.c_uint32)),
+                ("reservations", C.POINTER(CompileReservation)), ("discovered_memory", C.POINTER(C.c_int64)),
+                ("n_types", C.c_uint32), ("n_nodeclasses", C.c_uint32), ("n_all_zones", C.c_uint32),
+                ("n_unavailable", C.c_uint32), ("n_reservations", C.c_uint32), ("reserved_capacity", C.c_int32)]
+
+
+class CompileOut(C.Structure):
+    _fields_ = [("capacity", C.POINTER(ResourceList)), ("overhead", C.POINTER(ResourceList)),
+                ("kube_reserved", C.POINTER(ResourceList)), ("system_reserved", C.POINTER(ResourceList)),
+                ("eviction_threshold", C.POINTER(ResourceList)), ("it_zones", C.POINTER(C.c_uint64)),
+                ("price", C.POINTER(C.c_double)), ("available", C.POINTER(C.c_uint64)),
+                ("reserved", C.POINTER(ReservedOffering))]
+
+
+COMPILE_LISTS = ("capacity", "overhead", "kube_reserved", "system_reserved", "eviction_threshold")
+COMPILE_OUTPUTS = COMPILE_LISTS + ("it_zones", "price", "available", "reserved")
+CAPACITY_TYPES = ("on-demand", "spot")  # KP_CT_ON_DEMAND, KP_CT_SPOT
+
+
+def resource_list_dtype():
+    """kp_resource_list as a numpy record (tables of them come back from kp_catalog_compile)"""
+    import numpy as np
+    return np.dtype([("milli", "<i8", (NUM_RES,)), ("present", "<u4"), ("reserved_", "<u4")])
+
+
+def reserved_offering_dtype():
+    import numpy as np
+    return np.dtype([("price", "<f8"), ("available", "<i4"), ("capacity", "<i4")])
+
+
 # enum kp_validity
 (VALID, INVALID_UNSCHEDULED, INVALID_NO_REPLACEMENT_NEEDED, INVALID_MULTIPLE, INVALID_NEEDS_REPLACEMENT,
  INVALID_NOT_SUBSET, INVALID_BUDGET) = range(7)

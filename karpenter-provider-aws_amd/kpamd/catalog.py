@@ -6,6 +6,8 @@
                            computed behind the C ABI by kp_instance_type_resolve (libkp)
   create_offerings()       R:pkg/providers/instancetype/offering/offering.go:101-150 createOfferings
                            with pricing lookups R:pkg/providers/pricing/pricing.go:145-170
+  build_catalogs()         the same InstanceType lists for every EC2NodeClass from one kp_catalog_compile call
+                           (capacity, overhead and the offerings computed on the device)
 
 Synthetic pricing: on-demand from the static us-east-1 table; spot = OD × U(0.3, 0.7)
 per (type, zone) from splitmix64(seed=20250704), in table order then zone order.
@@ -294,6 +296,66 @@ def spot_price_table(rows, zones=ZONES, seed=SPOT_SEED):
             u = g.uniform()
             out[(r["name"], z)] = (r["od_price"] if r["od_price"] >= 0 else 0.0) * (0.3 + 0.4 * u)
     return out
+
+
+def default_spot_prices(rows, zones=ZONES, seed=SPOT_SEED):
+    """spot_price_table without the types that have no on-demand price: in the synthetic pricing those have no spot
+    price either (create_offerings' hasPrice), and a missing key is how Context.compile_catalogs is told so."""
+    unpriced = {r["name"] for r in rows if r["od_price"] < 0}
+    return {k: v for k, v in spot_price_table(rows, zones, seed).items() if k[0] not in unpriced}
+
+
+def build_catalogs(ctx, nodeclasses, rows=None, all_zones=ZONES, type_zones=None, spot_prices=None,
+                   unavailable=frozenset(), discovered_memory=None, reserved_capacity=True, opts=None):
+    """GetInstanceTypes for every EC2NodeClass from one kp_catalog_compile call (Context.compile_catalogs).
+    nodeclasses: one dict per EC2NodeClass of build_catalog's per-NodeClass keyword arguments (max_pods,
+    pods_per_core, zones, zone_ids, kubelet_cfg, capacity_reservations, ami_family, block_device_mappings,
+    instance_store_policy). The other arguments are shared: all_zones is the provider's zones (createOfferings
+    iterates them: an offering in a zone outside a NodeClass's subnets is never available and has no zone id),
+    type_zones the zones each row is offered in as bits over all_zones. Returns one InstanceType list per NodeClass,
+    each of the shape build_catalog returns; only compute_requirements (the label half) runs here."""
+    rows = load_ec2_table() if rows is None else rows
+    all_zones = list(all_zones)
+    ncs = [dict(kw) for kw in nodeclasses]
+    crs = [list(kw.pop("capacity_reservations", ())) for kw in ncs]
+    by_name = {r["name"]: t for t, r in enumerate(rows)}
+    tab = ctx.compile_catalogs(rows, ncs,
+                               all_zones=all_zones, type_zones=type_zones, spot_prices=spot_prices,
+                               unavailable=unavailable, reservations=crs, discovered_memory=discovered_memory,
+                               reserved_capacity=reserved_capacity, opts=opts)
+    price = tab["price"]
+    out = []
+    r0 = 0
+    for n, kw in enumerate(ncs):
+        zones, zone_ids = kw.get("zones", ZONES), kw.get("zone_ids", ZONE_IDS)
+        zid = dict(zip(zones, zone_ids))
+        reserved = {}  # type index -> [(reservation, record)] in the NodeClass's order
+        n_res = len(crs[n]) if reserved_capacity else 0
+        for j in range(n_res):
+            reserved.setdefault(by_name[crs[n][j].instance_type], []).append((crs[n][j], tab["reserved"][r0 + j]))
+        r0 += n_res
+        its = []
+        for t, r in enumerate(rows):
+            itz = int(tab["it_zones"][n, t])
+            mine = reserved.get(t, [])
+            reqs = compute_requirements(r, zones=zones, zone_ids=zone_ids,
+                                        offering_zones=[z for i, z in enumerate(all_zones) if itz >> i & 1],
+                                        reservations=[cr for cr, _ in mine], ami_family=kw.get("ami_family", "AL2023"))
+            avail = [int(a) for a in tab["available"][n, t]]
+            offs = [Offering(ct, z, zid.get(z), float(price[t, i, c]), bool(avail[c] >> i & 1))
+                    for i, z in enumerate(all_zones) for c, ct in enumerate(abi.CAPACITY_TYPES)]
+            offs += [Offering("reserved", cr.availability_zone, zid.get(cr.availability_zone), float(rec["price"]),
+                              bool(rec["available"]), cr.id, cr.reservation_type, int(rec["capacity"])) for cr, rec in mine]
+            its.append(InstanceType(r["name"], reqs, _record_dict(tab["capacity"][n, t]),
+                                    _record_dict(tab["overhead"][n, t]), offs))
+        out.append(its)
+    return out
+
+
+def _record_dict(rec):
+    """resource_dict of one abi.resource_list_dtype() record"""
+    present = int(rec["present"])
+    return {abi.RES_NAMES[i]: int(rec["milli"][i]) for i in range(abi.NUM_RES) if present & (1 << i)}
 
 
 def build_catalog(lib, rows=None, opts=None, max_pods=None, pods_per_core=None, zones=ZONES, zone_ids=ZONE_IDS,
