@@ -19,6 +19,9 @@
  *                             (R:pkg/providers/instance/instance.go:117-125 Create -> filterInstanceTypes :242-270,
  *                              getCapacityType :504-518, checkODFallback :336-355, getOverrides :392-439), batched:
  *                             one row per NodeClaim being launched.
+ *   kp_launch_templates    <- the same followed by getLaunchTemplateConfigs (R:instance.go:356-388): the grouping of
+ *                             MapToInstanceTypes (R:pkg/providers/amifamily/ami.go:222-235) and DefaultResolver.Resolve
+ *                             (R:pkg/providers/amifamily/resolver.go:126-188) with each template's overrides.
  *   kp_solve               <- upstream scheduling.Scheduler.Solve (sigs.k8s.io/karpenter
  *                             pkg/controllers/provisioning/scheduling/scheduler.go), reached from
  *                             R:pkg/providers/instancetype/suite_test.go:93,279 (NewProvisioner/ExpectProvisioned),
@@ -671,7 +674,9 @@ int32_t kp_filter_refresh(kp_filter_plan* plan, const kp_catalog* cat);
  * checkODFallback (R:instance.go:336-355): on-demand launch while flexible to spot with < 5 types (a warning);
  * getOverrides (R:instance.go:392-439): per remaining type (in truncated order) its available offerings compatible
  *   with the requirements narrowed to the chosen capacity type, in the type's offering order, whose zone has a
- *   subnet (subnet_zones stands for ZonalSubnetsForLaunch); launch-template grouping by AMI is AWS I/O, out of scope. */
+ *   subnet (subnet_zones stands for ZonalSubnetsForLaunch). Grouping the types and overrides into launch-template
+ *   configs by AMI, max-pods, EFA count and reservation is kp_launch_templates (below); creating the EC2 launch
+ *   template and hashing its name are AWS I/O, out of scope. */
 typedef struct kp_launch_request {
   kp_requirements requirements;   /* NodeClaim.Spec.Requirements (minValues allowed) */
   kp_resource_list requests;      /* NodeClaim.Spec.Resources.Requests */
@@ -1630,6 +1635,91 @@ typedef struct kp_compile_out {       /* caller-allocated; any may be NULL */
   kp_reserved_offering* reserved;     /* n_reservations */
 } kp_compile_out;
 int32_t kp_catalog_compile(kp_ctx* ctx, const kp_compile_in* in, const kp_compile_out* out, kp_solve_stats* stats);
+
+/* ---- launch-template configs (the CreateFleet LaunchTemplateConfigs of a burst of NodeClaims) ----------------
+ * kp_launch_templates = kp_launch_select followed, on the device, by the grouping that decides which launch templates
+ * a NodeClaim needs and which overrides each carries: amifamily.MapToInstanceTypes (R:pkg/providers/amifamily/
+ * ami.go:222-235), DefaultResolver.Resolve's grouping (R:pkg/providers/amifamily/resolver.go:126-188, 265-302) and
+ * getLaunchTemplateConfigs / getOverrides (R:pkg/providers/instance/instance.go:356-439). `amis` is the
+ * EC2NodeClass's status.amis in status order; one call covers one catalogue, that is one NodeClass.
+ *
+ * The rule, per request whose launch status is KP_LAUNCH_OK:
+ *  1. For each selected type, in truncated launch order, ami(t) is the first AMI in list order for which
+ *     type.Requirements.Compatible(NewNodeSelectorRequirements(ami.requirements...)) holds, with no well-known-label
+ *     allowance (kp_cluster_detect_drift's AMI judgement). A type no AMI takes belongs to no template (n_unmapped).
+ *  2. The group key is (ami(t), maxPods, efaCount, reservation part): maxPods = Capacity.Pods().Value(); efaCount =
+ *     Capacity[vpc.amazonaws.com/efa].Value() when the request's resource list carries that key (a present zero
+ *     counts: Go tests the key), else 0; the reservation part is empty unless the chosen capacity type is reserved.
+ *  3. Not reserved: one config per group. Its types are the group's members in launch order; its overrides are, for
+ *     each member in that order, the type's available offerings compatible with the requirements narrowed to the
+ *     capacity type, in the type's offering order, whose zone has a subnet: the type's entries of kp_launch_run's list.
+ *  4. Reserved: the reservation part is the reserved offerings of the type's offering slice as the launch filters left
+ *     it (one per zone after ReservedOfferingFilter), so every type is a group of its own (reservation ids are not
+ *     shared across instance types, the invariant resolver.go:174-176 relies on), and there is one config per (type,
+ *     reservation) in the type's offering order. Its overrides are only that reservation's offering: available,
+ *     compatible, zone with a subnet. reservation_type is that of the slice's reserved offerings.
+ *  5. A config without overrides is dropped (n_dropped). If none is left the status is KP_LT_NO_OFFERINGS, Go's "no
+ *     capacity offerings are currently available given the constraints".
+ *  6. Config order. Go iterates two maps here, so upstream's order is random and CreateFleet does not depend on it.
+ *     The order written here is canonical, not upstream's: by the launch-order position of a config's first type,
+ *     then by reservation in the type's offering order.
+ * The launch template's name (a hash of its options), user data, block-device and metadata defaults and
+ * ensureLaunchTemplate are AWS I/O and stay with the caller, which keys its template cache by the config record.
+ *
+ * Outputs, per request i (stride = max_types * max(1, n_subnet_zones), the override stride of kp_launch_run; it bounds
+ * the config count, every config that is kept having at least one override):
+ *   out, out_types                   exactly what kp_launch_run writes, bit for bit
+ *   lt_out[i]                        status, configs kept, selected types no AMI took, configs dropped
+ *   out_type_config[i][max_types]    per selected type (launch order) its first config, or -1 (unmapped, or every
+ *                                    config of it dropped); -1 past n_types
+ *   out_configs[i][stride]           n_configs records in canonical order
+ *   out_overrides[i][stride]         (type_index << 8) | zone as kp_launch_run; each config's entries are contiguous
+ *                                    [first_override, + n_overrides) and in getOverrides order. Not the list
+ *                                    kp_launch_run writes: that one is flat, in launch order
+ * A config's types: reservation_offering < 0: the selected types whose out_type_config is the config, in launch
+ * order; else the one type of its override. Entries past the counts are unspecified. Any output may be NULL.
+ *
+ * Errors: KP_E_INVAL for a NULL array whose count is not 0, an AMI with a NULL id, NULL requirement items, keys, value
+ * arrays or values, an operator outside kp_operator; those of kp_launch_select / kp_launch_run, the stale-plan refusal
+ * after kp_catalog_update_offerings until kp_launch_refresh among them. KP_E_UNSUPPORTED (the Go path then runs) for
+ * more than 65,535 AMIs (decided from the count before any array is read) and, for an instance type some
+ * request lists with a NotIn / Exists / Gt / Lt requirement, a pods capacity outside [0, 2^31) or an EFA capacity
+ * outside [0, 65535]. kp_launch_templates_validate checks `amis` alone, on the host, without a context. stats as
+ * kp_launch_run, device_ms covering launch_kernel and the two template kernels; prepare_ms is this call's host compile of the AMIs. */
+enum kp_lt_status {
+  KP_LT_OK = 0,
+  KP_LT_SKIPPED = 1,           /* the launch status is not KP_LAUNCH_OK: the launch result passes through, no configs */
+  KP_LT_NO_AMIS = 2,           /* n_amis == 0: "no amis exist given constraints" */
+  KP_LT_NO_COMPATIBLE_AMI = 3, /* no selected type maps to an AMI: "no instance types satisfy requirements of amis" */
+  KP_LT_NO_OFFERINGS = 4       /* every config was dropped */
+};
+typedef struct kp_lt_result {
+  int32_t status;              /* enum kp_lt_status */
+  uint32_t n_configs;
+  uint32_t n_unmapped;         /* selected types no AMI took */
+  uint32_t n_dropped;          /* configs dropped for having no override */
+} kp_lt_result;
+typedef struct kp_lt_config {
+  int32_t ami;                 /* index into amis */
+  int32_t max_pods;
+  int32_t efa_count;
+  int32_t reservation_offering;/* reserved launch: index of the reservation's offering in the type's
+                                  kp_instance_type.offerings (its reservation_id names the launch template's
+                                  CapacityReservationID); else -1 */
+  int32_t reservation_type;    /* reserved launch: 0 default, 1 capacity-block, -1 none; else -1 */
+  uint32_t first_override;     /* into out_overrides[i] */
+  uint32_t n_overrides;        /* > 0 */
+  uint32_t n_types;            /* > 0; 1 on a reserved launch */
+} kp_lt_config;
+int32_t kp_launch_templates_validate(const kp_ami* amis, uint32_t n_amis);
+int32_t kp_launch_run_templates(kp_launch_plan* plan, const kp_ami* amis, uint32_t n_amis, kp_launch_result* out,
+                                uint32_t* out_types, kp_lt_result* lt_out, int32_t* out_type_config,
+                                kp_lt_config* out_configs, uint32_t* out_overrides, kp_solve_stats* stats);
+int32_t kp_launch_templates(kp_ctx* ctx, const kp_catalog* cat, const kp_launch_request* reqs, uint32_t n,
+                            const char* const* subnet_zones, uint32_t n_subnet_zones, uint32_t max_types,
+                            const kp_ami* amis, uint32_t n_amis, kp_launch_result* out, uint32_t* out_types,
+                            kp_lt_result* lt_out, int32_t* out_type_config, kp_lt_config* out_configs,
+                            uint32_t* out_overrides, kp_solve_stats* stats);
 
 /* The reduction kp_consolidate_argmin applies to the gathered per-rank records (host-only; exposed for callers that
  * reduce over another transport, and for tests): counts are summed, the best record wins. */

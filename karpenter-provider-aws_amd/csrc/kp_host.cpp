@@ -34,6 +34,7 @@
 #include "kp_cand.h"
 #include "kp_catcomp.h"
 #include "kp_driftdet.h"
+#include "kp_ltgroup.h"
 #include "kp_schedin.h"
 #include "kp_device.h"
 #include "kp_model.h"
@@ -4651,6 +4652,7 @@ static void FillReservationTables(const Dict& d, const vector<HostType>& types, 
     }
 }
 
+struct LtState;  // kp_launch_templates (below)
 struct kp_launch_plan {
   CtxRef ctx;
   DevBuf buf;
@@ -4664,6 +4666,11 @@ struct kp_launch_plan {
   int T = 0;
   Compiled cp;
   CatOffsets coff{};
+  // kp_launch_run_templates: which requests list vpc.amazonaws.com/efa, the distinct types the requests list, and the
+  // state its first call builds
+  vector<uint8_t> req_efa;
+  vector<uint32_t> used;
+  std::shared_ptr<LtState> lt;
 };
 static_assert(sizeof(LaunchOut) == sizeof(kp_launch_result), "LaunchOut mirrors kp_launch_result");
 
@@ -4826,6 +4833,14 @@ int32_t kp_launch_prepare(kp_ctx* ctx, const kp_catalog* cat, const kp_launch_re
   plan->n = n;
   plan->max_types = max_types;
   plan->ovr_stride = ovr_stride;
+  plan->req_efa.resize(n);
+  for (uint32_t i = 0; i < n; i++) plan->req_efa[i] = (reqs[i].requests.present >> KP_RES_EFA) & 1;
+  {
+    vector<uint8_t> listed(std::max(T, 1), 0);
+    for (uint32_t j = 0; j < off[n]; j++) listed[list[j]] = 1;
+    for (int t = 0; t < T; t++)
+      if (listed[t]) plan->used.push_back((uint32_t)t);
+  }
   plan->cat = cat;
   plan->alive = cat->alive;
   plan->seqnum = cat->seqnum;
@@ -8496,13 +8511,42 @@ int32_t MergeReqs(const kp_requirements& r, std::map<string, SReq>& out) {
 }
 }  // namespace
 
-struct DriftState {
+// The dictionary of a set of instance types' requirements (an AMI's requirements are compiled against it)
+struct TypeDict {
+  std::unordered_map<string, uint32_t> tkey_id;           // keys of the types' requirements
+  vector<std::unordered_map<string, uint32_t>> tval_id;   // per such key the values some type holds
+  vector<vector<string>> tvals;                           // the same by id
+};
+// Each type's requirements merged per key, their keys and values entered into d
+static int32_t TypeRows(const vector<const HostType*>& types, TypeDict& d, vector<std::map<string, SReq>>& treqs) {
+  treqs.assign(types.size(), {});
+  for (size_t u = 0; u < types.size(); u++) {
+    const HostType& ht = *types[u];
+    for (const RawReq& r : ht.reqs) {
+      const char* none = nullptr;
+      vector<const char*> vp;
+      for (auto& v : r.values) vp.push_back(v.c_str());
+      kp_requirement q{r.key.c_str(), r.op, -1, vp.empty() ? &none : vp.data(), (uint32_t)vp.size(), 0};
+      const SReq s = SReqOf(q);
+      auto ins = treqs[u].emplace(Normalize(r.key), s);
+      if (!ins.second) ins.first->second = SReqMerge(s, ins.first->second);
+    }
+    for (auto& kv : treqs[u]) {
+      if (kv.second.complement)
+        return fail(KP_E_UNSUPPORTED, "instance type %s: a NotIn / Exists / Gt / Lt requirement on %s", ht.name.c_str(), kv.first.c_str());
+      const uint32_t k = d.tkey_id.emplace(kv.first, (uint32_t)d.tkey_id.size()).first->second;
+      if (k >= d.tval_id.size()) d.tval_id.resize(k + 1), d.tvals.resize(k + 1);
+      for (auto& v : kv.second.values)
+        if (d.tval_id[k].emplace(v, (uint32_t)d.tval_id[k].size()).second) d.tvals[k].push_back(v);
+    }
+  }
+  return KP_OK;
+}
+
+struct DriftState : TypeDict {                            // (the dictionary of the used types)
   DevBuf buf;
   DriftDetArgs a{};                                          // the resident half of the kernel arguments
   vector<vector<uint32_t>> pool_types;                    // per pool the distinct used types its nodes run
-  std::unordered_map<string, uint32_t> tkey_id;           // keys of the used types' requirements
-  vector<std::unordered_map<string, uint32_t>> tval_id;   // per such key the values some used type holds
-  vector<vector<string>> tvals;                           // the same by id
   DevBuf call;
   size_t call_bytes = 0;
 };
@@ -8610,27 +8654,10 @@ static int32_t DriftBuild(kp_cluster_plan* plan) {
   ds->pool_types.resize(P);
   for (uint32_t p = 0; p < P; p++) ds->pool_types[p].assign(pool_types[p].begin(), pool_types[p].end());
   // the used types' requirement rows: keys, per key the values some used type holds, per (type, key) the held set
-  vector<std::map<string, SReq>> treqs(U);
-  for (uint32_t u = 0; u < U; u++) {
-    const HostType& ht = cl.catalogs[used_list[u].first]->types[used_list[u].second];
-    for (const RawReq& r : ht.reqs) {
-      const char* none = nullptr;
-      vector<const char*> vp;
-      for (auto& v : r.values) vp.push_back(v.c_str());
-      kp_requirement q{r.key.c_str(), r.op, -1, vp.empty() ? &none : vp.data(), (uint32_t)vp.size(), 0};
-      const SReq s = SReqOf(q);
-      auto ins = treqs[u].emplace(Normalize(r.key), s);
-      if (!ins.second) ins.first->second = SReqMerge(s, ins.first->second);
-    }
-    for (auto& kv : treqs[u]) {
-      if (kv.second.complement)
-        return fail(KP_E_UNSUPPORTED, "instance type %s: a NotIn / Exists / Gt / Lt requirement on %s", ht.name.c_str(), kv.first.c_str());
-      const uint32_t k = ds->tkey_id.emplace(kv.first, (uint32_t)ds->tkey_id.size()).first->second;
-      if (k >= ds->tval_id.size()) ds->tval_id.resize(k + 1), ds->tvals.resize(k + 1);
-      for (auto& v : kv.second.values)
-        if (ds->tval_id[k].emplace(v, (uint32_t)ds->tval_id[k].size()).second) ds->tvals[k].push_back(v);
-    }
-  }
+  vector<std::map<string, SReq>> treqs;
+  vector<const HostType*> used_types(U);
+  for (uint32_t u = 0; u < U; u++) used_types[u] = &cl.catalogs[used_list[u].first]->types[used_list[u].second];
+  if (int32_t rc = TypeRows(used_types, *ds, treqs)) return rc;
   const uint32_t TK = (uint32_t)ds->tkey_id.size();
   if (TK > DR_TOK_KEY) return fail(KP_E_UNSUPPORTED, "%u distinct keys over the instance types (max 2^24 - 1)", TK);
   vector<uint32_t> tkey_off(std::max<uint32_t>(TK, 1), 0);
@@ -8673,8 +8700,8 @@ static int32_t DriftBuild(kp_cluster_plan* plan) {
   return KP_OK;
 }
 
-// One AMI's requirements as tokens over the used types' dictionary (kp_driftdet.h)
-static void DriftCompileAmi(const DriftState& ds, const std::map<string, SReq>& reqs, vector<uint32_t>& tok) {
+// One AMI's requirements as tokens over the types' dictionary (kp_driftdet.h)
+static void DriftCompileAmi(const TypeDict& ds, const std::map<string, SReq>& reqs, vector<uint32_t>& tok) {
   const size_t start = tok.size();
   for (auto& kv : reqs) {
     const SReq& r = kv.second;
@@ -8861,6 +8888,183 @@ int32_t kp_cluster_detect_drift(kp_cluster_plan* plan, const kp_drift_in* in, kp
     stats->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
   return KP_OK;
+}
+
+}  // extern "C"
+
+// ---- Launch-template configs (kp_launch_templates) ------------------------------------------------------------------
+// The host does strings only. Once per launch plan (LtBuild): the requirement rows of the types its requests list against
+// their own dictionary, laid out for lanes over types. Per call: the AMI requirements compiled into kp_driftdet.h's
+// tokens against that dictionary; an AMI is its index. The selection never comes back to the host between launch_kernel
+// and the grouping (kp_ltgroup.hip).
+static_assert(sizeof(LtOut) == sizeof(kp_lt_result) && sizeof(LtConfig) == sizeof(kp_lt_config),
+              "the device records mirror the ABI's");
+
+struct LtState : TypeDict {
+  DevBuf buf;  // the resident tables, ami_of and the four outputs
+  LtArgs a{};
+  DevBuf call;  // the call's AMI tokens
+  size_t call_bytes = 0;
+};
+
+static int32_t LtCheckAmis(const kp_ami* amis, uint32_t n_amis) {
+  if (n_amis > LT_MAX_AMIS) return fail(KP_E_UNSUPPORTED, "%u AMIs (max %d)", n_amis, LT_MAX_AMIS);
+  if (n_amis && !amis) return fail(KP_E_INVAL, "null amis");
+  for (uint32_t j = 0; j < n_amis; j++) {
+    if (!amis[j].id) return fail(KP_E_INVAL, "AMI %u has a null id", j);
+    if (int32_t rc = CheckReqs(amis[j].requirements, "AMI", 0, j)) return rc;
+  }
+  return KP_OK;
+}
+
+static int32_t LtBuild(kp_launch_plan* plan) {
+  kp_ctx* ctx = plan->ctx;
+  const uint32_t T = (uint32_t)plan->T, n = plan->n;
+  auto ls = std::make_shared<LtState>();
+  // only the types some request lists: no other row is read, and a type nobody lists refuses nothing
+  const vector<uint32_t>& used = plan->used;
+  vector<const HostType*> types(used.size());
+  for (size_t u = 0; u < used.size(); u++) {
+    const HostType& ht = plan->cat->types[used[u]];
+    types[u] = &ht;
+    const int64_t pods = ((ht.cap_present >> KP_RES_PODS) & 1) ? ht.cap[KP_RES_PODS] : 0;
+    const int64_t efa = ((ht.cap_present >> KP_RES_EFA) & 1) ? ht.cap[KP_RES_EFA] : 0;
+    if (pods < 0 || pods > 0x7FFFFFFFll * 1000) return fail(KP_E_UNSUPPORTED, "instance type %s: pods capacity %lld", ht.name.c_str(), (long long)pods);
+    if (efa < 0 || efa > 65535ll * 1000) return fail(KP_E_UNSUPPORTED, "instance type %s: EFA capacity %lld", ht.name.c_str(), (long long)efa);
+  }
+  vector<std::map<string, SReq>> treqs;
+  if (int32_t rc = TypeRows(types, *ls, treqs)) return rc;
+  const uint32_t TK = (uint32_t)ls->tkey_id.size();
+  vector<uint32_t> tkey_off(std::max<uint32_t>(TK, 1), 0);
+  size_t TW = 0;
+  for (uint32_t k = 0; k < TK; k++) {
+    tkey_off[k] = (uint32_t)TW;
+    TW += std::max<size_t>(1, (ls->tvals[k].size() + 63) / 64);
+  }
+  // (T <= 4096 on a launch plan; a key has at most T * values-per-type values)
+  if (TW * std::max<uint32_t>(T, 1) > 0x7FFFFFFFull) return fail(KP_E_UNSUPPORTED, "the instance types' requirement table is too large");
+  vector<uint32_t> type_cnt((size_t)TK * T, DR_NONE);
+  vector<uint64_t> type_bits(TW * T, 0);
+  for (size_t u = 0; u < used.size(); u++)
+    for (auto& kv : treqs[u]) {
+      const uint32_t k = ls->tkey_id[kv.first], t = used[u];
+      type_cnt[(size_t)k * T + t] = (uint32_t)kv.second.values.size();
+      for (auto& v : kv.second.values) {
+        const uint32_t id = ls->tval_id[k][v];
+        type_bits[((size_t)tkey_off[k] + (id >> 6)) * T + t] |= 1ull << (id & 63);
+      }
+    }
+  const size_t n1 = std::max<uint32_t>(n, 1);
+  Blob blob;
+  const size_t o_tcnt = blob.put(type_cnt), o_tbits = blob.put(type_bits), o_toff = blob.put(tkey_off),
+               o_used = blob.put(plan->used), o_efa = blob.put(plan->req_efa);
+  const size_t o_amiof = blob.reserve_dev(sizeof(uint32_t) * std::max<uint32_t>(T, 1)),
+               o_lt = blob.reserve_dev(sizeof(LtOut) * n1),
+               o_tc = blob.reserve_dev(sizeof(int32_t) * n1 * plan->max_types),
+               o_cfg = blob.reserve_dev(sizeof(LtConfig) * n1 * plan->ovr_stride),
+               o_ovr = blob.reserve_dev(sizeof(uint32_t) * n1 * plan->ovr_stride);
+  HIPCHK(ls->buf.alloc(blob.total()));
+  uint8_t* base = (uint8_t*)ls->buf.p;
+  HIPCHK(hipMemcpyAsync(base, blob.host.data(), blob.host.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  LtArgs& a = ls->a;
+  a.type_cnt = (const uint32_t*)(base + o_tcnt), a.type_bits = (const uint64_t*)(base + o_tbits);
+  a.tkey_off = (const uint32_t*)(base + o_toff), a.used = (const uint32_t*)(base + o_used);
+  a.req_efa = base + o_efa;
+  a.T = (int32_t)T, a.n_tkeys = (int32_t)TK, a.type_words = (int32_t)TW, a.n_used = (int32_t)plan->used.size();
+  a.ami_of = (uint32_t*)(base + o_amiof), a.lt_out = (LtOut*)(base + o_lt), a.type_config = (int32_t*)(base + o_tc);
+  a.configs = (LtConfig*)(base + o_cfg), a.overrides = (uint32_t*)(base + o_ovr);
+  plan->lt = std::move(ls);
+  return KP_OK;
+}
+
+extern "C" {
+
+int32_t kp_launch_templates_validate(const kp_ami* amis, uint32_t n_amis) { return LtCheckAmis(amis, n_amis); }
+
+// kp_launch_run followed by the template kernels on the same stream; results copied only into the non-NULL buffers.
+int32_t kp_launch_run_templates(kp_launch_plan* plan, const kp_ami* amis, uint32_t n_amis, kp_launch_result* out,
+                                uint32_t* out_types, kp_lt_result* lt_out, int32_t* out_type_config,
+                                kp_lt_config* out_configs, uint32_t* out_overrides, kp_solve_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (!plan) return fail(KP_E_INVAL, "null argument");
+  kp_ctx* ctx = plan->ctx;
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  if (int32_t rc = CatalogsAlive({plan->alive})) return rc;
+  if (plan->cat->seqnum != plan->seqnum)
+    return fail(KP_E_INVAL, "stale plan: catalogue seqnum %llu, plan built at %llu (kp_launch_refresh)",
+                (unsigned long long)plan->cat->seqnum, (unsigned long long)plan->seqnum);
+  if (int32_t rc = LtCheckAmis(amis, n_amis)) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!plan->lt)
+    if (int32_t rc = LtBuild(plan)) return rc;
+  LtState& ls = *plan->lt;
+  const auto t1 = std::chrono::steady_clock::now();
+  vector<uint32_t> tok_off(1, 0), tok;
+  for (uint32_t j = 0; j < n_amis; j++) {
+    std::map<string, SReq> merged;
+    MergeReqs(amis[j].requirements, merged);
+    DriftCompileAmi(ls, merged, tok);
+    if (tok.size() >= (1ull << 31)) return fail(KP_E_UNSUPPORTED, "2^31 or more AMI terms");
+    tok_off.push_back((uint32_t)tok.size());
+  }
+  Blob blob;
+  const size_t o_toff = blob.put(tok_off), o_tok = blob.put(tok);
+  if (blob.total() > ls.call_bytes) {
+    HIPCHK(ls.call.alloc(blob.total()));
+    ls.call_bytes = blob.total();
+  }
+  const double compile_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+  hipStream_t st = ctx->stream;
+  uint8_t* cb = (uint8_t*)ls.call.p;
+  LtArgs a = ls.a;
+  a.la = plan->la;
+  a.ami_tok_off = (const uint32_t*)(cb + o_toff), a.ami_tok = (const uint32_t*)(cb + o_tok);
+  a.n_amis = (int32_t)n_amis;
+  uint8_t* base = (uint8_t*)plan->buf.p;
+  const uint32_t n = plan->n;
+  HIPCHK(hipMemcpyAsync(cb, blob.host.data(), blob.host.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(a.ami_of, 0xFF, sizeof(uint32_t) * std::max<int32_t>(a.T, 1), st));  // DR_NONE
+  HIPCHK(hipMemsetAsync(base + plan->o_stats, 0, sizeof(uint64_t) * 2, st));
+  HIPCHK(hipEventRecord(ctx->ev0, st));
+  if (n) HIPCHK(launch_launch(plan->la, st));
+  if (n) HIPCHK(launch_lt(a, st));
+  HIPCHK(hipEventRecord(ctx->ev1, st));
+  uint64_t ls_st[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(ls_st, base + plan->o_stats, sizeof ls_st, hipMemcpyDeviceToHost, st));
+  const size_t nt = (size_t)n * plan->max_types, no = (size_t)n * plan->ovr_stride;
+  if (n && out) HIPCHK(hipMemcpyAsync(out, base + plan->o_out, sizeof(kp_launch_result) * n, hipMemcpyDeviceToHost, st));
+  if (n && out_types) HIPCHK(hipMemcpyAsync(out_types, base + plan->o_types, sizeof(uint32_t) * nt, hipMemcpyDeviceToHost, st));
+  if (n && lt_out) HIPCHK(hipMemcpyAsync(lt_out, a.lt_out, sizeof(LtOut) * n, hipMemcpyDeviceToHost, st));
+  if (n && out_type_config) HIPCHK(hipMemcpyAsync(out_type_config, a.type_config, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
+  if (n && out_configs) HIPCHK(hipMemcpyAsync(out_configs, a.configs, sizeof(LtConfig) * no, hipMemcpyDeviceToHost, st));
+  if (n && out_overrides) HIPCHK(hipMemcpyAsync(out_overrides, a.overrides, sizeof(uint32_t) * no, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  if (stats) {
+    memset(stats, 0, sizeof *stats);
+    stats->device_ms = ms;
+    stats->attempts = ls_st[0];
+    stats->bytes_algorithmic = ls_st[1];
+    stats->prepare_ms = compile_ms;  // this call's host compile (the AMI tokens); the first call also builds the type table
+    stats->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return KP_OK;
+}
+
+int32_t kp_launch_templates(kp_ctx* ctx, const kp_catalog* cat, const kp_launch_request* reqs, uint32_t n,
+                            const char* const* subnet_zones, uint32_t n_subnet_zones, uint32_t max_types,
+                            const kp_ami* amis, uint32_t n_amis, kp_launch_result* out, uint32_t* out_types,
+                            kp_lt_result* lt_out, int32_t* out_type_config, kp_lt_config* out_configs,
+                            uint32_t* out_overrides, kp_solve_stats* stats) {
+  if (int32_t rc = LtCheckAmis(amis, n_amis)) return rc;
+  kp_launch_plan* plan = nullptr;
+  int32_t rc = kp_launch_prepare(ctx, cat, reqs, n, subnet_zones, n_subnet_zones, max_types, &plan);
+  if (rc) return rc;
+  rc = kp_launch_run_templates(plan, amis, n_amis, out, out_types, lt_out, out_type_config, out_configs, out_overrides, stats);
+  kp_launch_plan_destroy(plan);
+  return rc;
 }
 
 }  // extern "C"

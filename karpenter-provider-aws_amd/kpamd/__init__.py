@@ -76,6 +76,13 @@ def load_lib(path=None):
         "kp_launch_select": (C.c_int32, [C.c_void_p, C.c_void_p, P(abi.LaunchRequest), C.c_uint32, P(C.c_char_p),
                                          C.c_uint32, C.c_uint32, P(abi.LaunchResult), P(C.c_uint32), P(C.c_uint32),
                                          P(abi.SolveStats)]),
+        "kp_launch_templates_validate": (C.c_int32, [P(abi.Ami), C.c_uint32]),
+        "kp_launch_run_templates": (C.c_int32, [C.c_void_p, P(abi.Ami), C.c_uint32, P(abi.LaunchResult), P(C.c_uint32),
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(abi.SolveStats)]),
+        "kp_launch_templates": (C.c_int32, [C.c_void_p, C.c_void_p, P(abi.LaunchRequest), C.c_uint32, P(C.c_char_p),
+                                            C.c_uint32, C.c_uint32, P(abi.Ami), C.c_uint32, P(abi.LaunchResult),
+                                            P(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            P(abi.SolveStats)]),
         "kp_solve": (C.c_int32, [C.c_void_p, P(abi.SolveIn), P(C.c_void_p)]),
         "kp_solve_validate": (C.c_int32, [P(abi.SolveIn)]),
         "kp_solve_prepare": (C.c_int32, [C.c_void_p, P(abi.SolveIn), P(C.c_void_p)]),
@@ -213,6 +220,21 @@ class Context:
         cin = build_compile_in(arena, opts or self.opts, rows, nodeclasses, all_zones, type_zones, spot_prices, unavailable,
                                reservations, discovered_memory, reserved_capacity)
         return _catalog_compile_raw(self.lib, self.h, cin, abi.COMPILE_OUTPUTS if outputs is None else outputs)
+
+    def launch_templates(self, catalog, requests, subnet_zones, amis, max_types=60):
+        """kp_launch_templates: the launch-side selection of each request followed by its CreateFleet launch-template
+        configs. Returns one dict per request: the launch_select fields (the flat override list replaced
+        by its length, n_overrides), lt_status, unmapped, dropped and configs [{ami, max_pods, efa_count,
+        reservation_id, reservation_type, types, overrides}] in canonical order."""
+        arena = Arena()
+        rq = abi.launch_requests(arena, requests)
+        zones = list(subnet_zones)
+        zs = arena.arr(C.c_char_p, [z.encode() for z in zones])
+        am, n_amis = abi.amis(arena, amis)
+        lib = self.lib
+        return _read_templates(lib, lambda *bufs: lib.kp_launch_templates(self.h, catalog.h, rq, len(requests), zs,
+                                                                          len(zones), max_types, am, n_amis, *bufs),
+                               len(requests), max_types, zones, amis, catalog.instance_types)[0]
 
     def close(self):
         if self.h:
@@ -714,6 +736,32 @@ class FilterPlan:
 MAX_LAUNCH_TYPES = 60  # maxInstanceTypes (R:pkg/providers/instance/instance.go:60)
 
 
+def _read_templates(lib, call, n, max_types, zones, amis, instance_types):
+    """Allocate kp_launch_templates' outputs, run call(out, out_types, lt_out, out_type_config, out_configs,
+    out_overrides, stats) and read them: ([dict per request], stats)."""
+    st = abi.SolveStats()
+    stride = max_types * max(1, len(zones))
+    out = (abi.LaunchResult * max(1, n))()
+    types = np.zeros(max(1, n * max_types), dtype=np.uint32)
+    lt = np.zeros(max(1, n), dtype=abi.lt_result_dtype())
+    tcfg = np.zeros(max(1, n * max_types), dtype=np.int32)
+    cfgs = np.zeros(max(1, n * stride), dtype=abi.lt_config_dtype())
+    ovr = np.zeros(max(1, n * stride), dtype=np.uint32)
+    _check(lib, call(out, types.ctypes.data_as(C.POINTER(C.c_uint32)), lt.ctypes.data, tcfg.ctypes.data, cfgs.ctypes.data,
+                     ovr.ctypes.data, C.byref(st)))
+    res = []
+    for i in range(n):
+        # (a launch result dict's overrides are kp_launch_run's flat list, which this call does not return: its length
+        # stays, the overrides are the configs')
+        base = abi.launch_result_dict(out[i], types[i * max_types:(i + 1) * max_types], ovr[:0], zones)
+        del base["overrides"]
+        base["n_overrides"] = int(out[i].n_overrides)
+        res.append(abi.launch_templates_dict(base, lt[i], tcfg[i * max_types:(i + 1) * max_types],
+                                             cfgs[i * stride:(i + 1) * stride], ovr[i * stride:(i + 1) * stride], zones,
+                                             amis, instance_types))
+    return res, stats_dict(st)
+
+
 class LaunchPlan:
     """kp_launch_prepare / kp_launch_run: instance.DefaultProvider.Create's launch-side selection for a batch of
     NodeClaims (filters, Truncate, capacity type, CreateFleet overrides), requests resident on the device.
@@ -721,6 +769,7 @@ class LaunchPlan:
 
     def __init__(self, ctx, catalog, requests, subnet_zones, max_types=MAX_LAUNCH_TYPES):
         self.ctx = ctx
+        self.catalog = catalog
         self.n = len(requests)
         self.zones = list(subnet_zones)
         self.max_types = max_types
@@ -748,6 +797,20 @@ class LaunchPlan:
         res = [abi.launch_result_dict(out[i], types[i * self.max_types:(i + 1) * self.max_types],
                                       ovr[i * stride:(i + 1) * stride], self.zones) for i in range(self.n)]
         return res, stats_dict(st)
+
+    def templates(self, amis, read=True):
+        """kp_launch_run_templates: one launch followed by the launch-template grouping on the device.
+        amis: the EC2NodeClass's status.amis ([model.AMI], status order). read=True returns ([the run() dict plus
+        lt_status, unmapped, dropped, configs per request], stats), else (None, stats)."""
+        st = abi.SolveStats()
+        lib, n = self.ctx.lib, self.n
+        arena = Arena()
+        am, n_amis = abi.amis(arena, amis)
+        if not read:
+            _check(lib, lib.kp_launch_run_templates(self.h, am, n_amis, None, None, None, None, None, None, C.byref(st)))
+            return None, stats_dict(st)
+        return _read_templates(lib, lambda *bufs: lib.kp_launch_run_templates(self.h, am, n_amis, *bufs), n, self.max_types,
+                               self.zones, amis, self.catalog.instance_types)
 
     def refresh(self, catalog):
         """kp_launch_refresh: re-apply the catalogue's current offerings (ICE / price) to the resident plan."""

@@ -641,6 +641,67 @@ def launch_result_dict(r, types, ovr, zones):
             "rejected_reservation": int(r.rejected_reservation)}
 
 
+class LtResult(C.Structure):
+    """kp_lt_result"""
+    _fields_ = [("status", C.c_int32), ("n_configs", C.c_uint32), ("n_unmapped", C.c_uint32), ("n_dropped", C.c_uint32)]
+
+
+class LtConfig(C.Structure):
+    """kp_lt_config"""
+    _fields_ = [("ami", C.c_int32), ("max_pods", C.c_int32), ("efa_count", C.c_int32),
+                ("reservation_offering", C.c_int32), ("reservation_type", C.c_int32), ("first_override", C.c_uint32),
+                ("n_overrides", C.c_uint32), ("n_types", C.c_uint32)]
+
+
+# enum kp_lt_status
+LT_OK, LT_SKIPPED, LT_NO_AMIS, LT_NO_COMPATIBLE_AMI, LT_NO_OFFERINGS = range(5)
+LT_STATUS_NAMES = ("OK", "SKIPPED", "NO_AMIS", "NO_COMPATIBLE_AMI", "NO_OFFERINGS")
+
+
+def lt_result_dtype():
+    import numpy as np
+    return np.dtype([("status", "<i4"), ("n_configs", "<u4"), ("n_unmapped", "<u4"), ("n_dropped", "<u4")])
+
+
+def lt_config_dtype():
+    import numpy as np
+    return np.dtype([("ami", "<i4"), ("max_pods", "<i4"), ("efa_count", "<i4"), ("reservation_offering", "<i4"),
+                     ("reservation_type", "<i4"), ("first_override", "<u4"), ("n_overrides", "<u4"), ("n_types", "<u4")])
+
+
+def amis(arena, amis):
+    """[model.AMI] -> (kp_ami array or None, count)"""
+    items = [Ami(arena.s(a.id), arena.requirements(a.requirements)) for a in amis]
+    return (arena.arr(Ami, items) if items else None), len(items)
+
+
+def launch_templates_dict(base, lt, type_config, configs, ovr, zones, amis, instance_types):
+    """One request's kp_launch_templates records -> the launch_select dict plus lt_status, unmapped, dropped and
+    configs [{ami, max_pods, efa_count, reservation_id, reservation_type, types, overrides}] in canonical order."""
+    out = dict(base)
+    out["lt_status"] = LT_STATUS_NAMES[int(lt["status"])]
+    out["unmapped"] = int(lt["n_unmapped"])
+    out["dropped"] = int(lt["n_dropped"])
+    sel, cfgs = base["types"], []
+    for c in range(int(lt["n_configs"])):
+        r = configs[c]
+        lo, n = int(r["first_override"]), int(r["n_overrides"])
+        ovs = [(int(o) >> 8, zones[int(o) & 0xFF]) for o in ovr[lo:lo + n]]
+        j = int(r["reservation_offering"])
+        if j >= 0:  # a reserved launch: the one type of the config's override
+            types = [ovs[0][0]]
+            rid = instance_types[types[0]].offerings[j].reservation_id
+        else:
+            types, rid = [t for i, t in enumerate(sel) if int(type_config[i]) == c], None
+        assert len(types) == int(r["n_types"])
+        cfgs.append({"ami": amis[int(r["ami"])].id, "max_pods": int(r["max_pods"]), "efa_count": int(r["efa_count"]),
+                     "reservation_id": rid,
+                     "reservation_type": {0: "default", 1: "capacity-block"}.get(int(r["reservation_type"])),
+                     "types": types, "overrides": ovs})
+    out["configs"] = cfgs
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # Marshalling: Python model objects (kpamd.model) -> ctypes, keeping every buffer alive on `self.keep`.
 # ------------------------------------------------------------------------------------------------
