@@ -1721,6 +1721,102 @@ int32_t kp_launch_templates(kp_ctx* ctx, const kp_catalog* cat, const kp_launch_
                             kp_lt_result* lt_out, int32_t* out_type_config, kp_lt_config* out_configs,
                             uint32_t* out_overrides, kp_solve_stats* stats);
 
+/* ---- interruption messages (which NodeClaims a batch of queue messages deletes, which spot offerings it marks) ----
+ * kp_cluster_interruptions resolves a whole batch of parsed interruption-queue messages against a prepared cluster
+ * plan's snapshot in one call: the interruption controller's handleMessage / handleNodeClaim / deleteNodeClaim
+ * (R:pkg/controllers/interruption/controller.go:160-248) for every message at once, where upstream does one List per
+ * instance id. Receiving, parsing and deleting the SQS messages, events, latency metrics and the API delete stay with
+ * the caller.
+ *
+ * Messages. A message is a kind (enum kp_message_kind) and a list of EC2 instance ids; only scheduled_change carries
+ * several. Kinds 2-5 act (actionForMessage, :272-279: CordonAndDrain), kind 1 only notifies, kind 0 is ignored before
+ * its ids are read (:164-166): its entries match nothing.
+ *
+ * Match. A (message, id) entry matches every node of the snapshot whose instance id (node_ids[n], the last path
+ * segment of the provider id, R:pkg/utils/utils.go:36-52) equals the id byte for byte. Several NodeClaims may share
+ * one id (handleMessage loops over Items); a node whose node_ids entry is NULL matches nothing.
+ *
+ * Per node, over its matching entries of kinds 1-5:
+ *   kinds          the OR of 1 << kind
+ *   n_messages     the number of entries: a message that names the id twice counts twice
+ *   first_message  the lowest message index among the matches of kinds 2-5, or -1. Upstream handles ten messages at a
+ *                  time, so which message deletes a NodeClaim hit by several is random there; the lowest index is the
+ *                  canonical choice.
+ *   flags          KP_INTERRUPT_DELETE            first_message >= 0 and kp_cluster_node.deleting == 0
+ *                  KP_INTERRUPT_ALREADY_DELETING  first_message >= 0 and the node is deleting: deleteNodeClaim returns
+ *                                                 early (:234-236), nothing is deleted or counted
+ *                  KP_INTERRUPT_ICE               the node carries an ICE mark, see below
+ *
+ * ICE marks (:218-225). A spot_interrupted match on a node whose labels node.kubernetes.io/instance-type and
+ * topology.kubernetes.io/zone are both present and non-empty marks (type label, zone label) unavailable for capacity
+ * type spot, whatever the node's own capacity type and whether or not it is deleting. Such a node carries the mark.
+ * Marks are de-duplicated by the two label strings (type names repeat across catalogues, and the reference's cache is
+ * keyed by name). A mark is returned as the lowest node index that carries it and the number of nodes that carry it;
+ * the caller reads the two labels from that node.
+ *
+ * Outputs (each of out_nodes, out_matches, deletes, marks, counts may be NULL to skip it):
+ *   out_nodes[n_nodes]    the per-node record above
+ *   out_matches[n_ids]    per (message, id) entry how many nodes it matched; 0: the id named no NodeClaim
+ *   deletes[<= n_nodes]   one record per node with KP_INTERRUPT_DELETE, in node order: the node, its first_message and
+ *                         that message's kind. *n_deletes receives the count
+ *   marks[<= n_nodes]     one record per distinct mark, in order of `node`. *n_marks receives the count
+ *   counts[6]             deletes per kind of first_message (NodeClaimsDisruptedTotal's reason)
+ *   stats                 device_ms (the kernels), host_ms (the call)
+ * Two calls with equal inputs on one plan write identical bytes.
+ *
+ * Inputs. kinds[n_messages]; the CSR id_offsets[n_messages + 1] over ids[n_ids] (id_offsets may be NULL when
+ * n_messages is 0); node_ids[n_nodes]. table_log2 0 lets the library size the join's hash table; any other value
+ * forces 1 << table_log2 slots, which must exceed the number of nodes that have an id (tests force long probe runs).
+ *
+ * Errors. KP_E_UNSUPPORTED for 2^31 or more messages or ids (decided from the counts before any array is read) and for
+ * an id longer than 31 bytes (EC2's are 19). KP_E_INVAL for a NULL argument, a NULL array whose count is not 0, a NULL
+ * message id, a kind outside 0-5, offsets that do not start at 0, decrease, or end elsewhere than n_ids, table_log2
+ * above 30 or a forced table that is too small; kp_interruptions_validate checks all of these on the host without a
+ * context. With a plan also: n_nodes different from the snapshot's node count, NULL n_deletes or n_marks, and the
+ * stale-plan refusal of kp_cluster_candidates. */
+enum kp_message_kind {
+  KP_MSG_NO_OP = 0,
+  KP_MSG_REBALANCE_RECOMMENDATION = 1,
+  KP_MSG_SCHEDULED_CHANGE = 2,
+  KP_MSG_SPOT_INTERRUPTED = 3,
+  KP_MSG_INSTANCE_STOPPED = 4,
+  KP_MSG_INSTANCE_TERMINATED = 5
+};
+#define KP_MESSAGE_KIND_COUNT 6
+#define KP_INTERRUPT_DELETE 1u
+#define KP_INTERRUPT_ALREADY_DELETING 2u
+#define KP_INTERRUPT_ICE 4u
+typedef struct kp_interrupt_node {
+  int32_t first_message;
+  uint32_t kinds;
+  uint32_t n_messages;
+  uint32_t flags;                     /* KP_INTERRUPT_* */
+} kp_interrupt_node;
+typedef struct kp_interrupt_delete {
+  uint32_t node;
+  uint32_t message;                   /* the node's first_message */
+  int32_t kind;                       /* enum kp_message_kind of that message */
+  uint32_t reserved;
+} kp_interrupt_delete;
+typedef struct kp_interrupt_mark {
+  uint32_t node;                      /* the lowest node that carries the mark */
+  uint32_t n_nodes;                   /* nodes that carry it */
+} kp_interrupt_mark;
+typedef struct kp_interrupt_in {
+  const int32_t* kinds;               /* n_messages, enum kp_message_kind */
+  const uint32_t* id_offsets;         /* n_messages + 1 */
+  const char* const* ids;             /* n_ids */
+  const char* const* node_ids;        /* n_nodes; NULL entry: the node has no provider id */
+  uint32_t n_messages;
+  uint32_t n_ids;
+  uint32_t n_nodes;
+  uint32_t table_log2;
+} kp_interrupt_in;
+int32_t kp_interruptions_validate(const kp_interrupt_in* in);
+int32_t kp_cluster_interruptions(kp_cluster_plan* plan, const kp_interrupt_in* in, kp_interrupt_node* out_nodes,
+                                 uint32_t* out_matches, kp_interrupt_delete* deletes, uint32_t* n_deletes,
+                                 kp_interrupt_mark* marks, uint32_t* n_marks, uint64_t* counts, kp_solve_stats* stats);
+
 /* The reduction kp_consolidate_argmin applies to the gathered per-rank records (host-only; exposed for callers that
  * reduce over another transport, and for tests): counts are summed, the best record wins. */
 int32_t kp_choice_reduce(const kp_choice* per_rank, uint32_t n, kp_choice* out);

@@ -34,6 +34,7 @@
 #include "kp_cand.h"
 #include "kp_catcomp.h"
 #include "kp_driftdet.h"
+#include "kp_interrupt.h"
 #include "kp_ltgroup.h"
 #include "kp_schedin.h"
 #include "kp_device.h"
@@ -5096,6 +5097,7 @@ struct CandState {
 };
 
 struct DriftState;
+struct InterruptState;
 struct GeneralBatch;
 struct kp_cluster_plan {
   CtxRef ctx;
@@ -5139,6 +5141,7 @@ struct kp_cluster_plan {
   uint32_t n_pools = 0;
   std::unique_ptr<CandState> cand;        // kp_cluster_candidates, built on its first call
   std::shared_ptr<DriftState> drift;      // kp_cluster_detect_drift, built on its first call
+  std::shared_ptr<InterruptState> interrupt;  // kp_cluster_interruptions, built on its first call
 };
 
 // kp_*_budgeted: the caller's allowed[] and the count of subsets it blocked
@@ -8881,6 +8884,204 @@ int32_t kp_cluster_detect_drift(kp_cluster_plan* plan, const kp_drift_in* in, kp
   if (counts) HIPCHK(hipMemcpyAsync(hist, a.counts, sizeof hist, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   if (counts) memcpy(counts, hist, sizeof hist);
+  if (stats) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    stats->device_ms = ms;
+    stats->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return KP_OK;
+}
+
+}  // extern "C"
+
+// ---- Interruption messages (kp_cluster_interruptions) ---------------------------------------------------------------
+// The host does strings only. Once per plan (InterruptBuild): each node's (instance-type label, zone label) pair
+// interned to an integer, resident with the deleting flags. Per call: every id copied into a zero-padded 32-byte slot.
+// The host builds no map over ids: the join, the fold and the two compactions are the device's (kp_interrupt.hip).
+static_assert(sizeof(IrNodeOut) == sizeof(kp_interrupt_node) && sizeof(IrDelete) == sizeof(kp_interrupt_delete) &&
+                  sizeof(IrMark) == sizeof(kp_interrupt_mark),
+              "the device records mirror the ABI's");
+
+struct InterruptState {
+  DevBuf buf;  // node_pair, node_deleting
+  InterruptArgs a{};
+  DevBuf call;
+  size_t call_bytes = 0;
+};
+
+// What needs no plan; *n_with_id receives the number of nodes that have an id
+static int32_t InterruptCheck(const kp_interrupt_in* in, uint32_t* n_with_id) {
+  if (!in) return fail(KP_E_INVAL, "null argument");
+  if (in->n_messages >= (1u << 31) || in->n_ids >= (1u << 31))
+    return fail(KP_E_UNSUPPORTED, "%u messages, %u ids (max 2^31 - 1 each)", in->n_messages, in->n_ids);
+  if (in->n_messages && (!in->kinds || !in->id_offsets)) return fail(KP_E_INVAL, "null kinds or id_offsets");
+  if (in->n_ids && !in->ids) return fail(KP_E_INVAL, "null ids");
+  if (in->n_nodes && !in->node_ids) return fail(KP_E_INVAL, "null node_ids");
+  if (in->table_log2 > 30) return fail(KP_E_INVAL, "table_log2 %u (max 30)", in->table_log2);
+  for (uint32_t m = 0; m < in->n_messages; m++)
+    if (in->kinds[m] < KP_MSG_NO_OP || in->kinds[m] > KP_MSG_INSTANCE_TERMINATED)
+      return fail(KP_E_INVAL, "message %u: kind %d", m, in->kinds[m]);
+  if (in->id_offsets) {
+    if (in->id_offsets[0] != 0) return fail(KP_E_INVAL, "id_offsets start at %u", in->id_offsets[0]);
+    for (uint32_t m = 0; m < in->n_messages; m++)
+      if (in->id_offsets[m + 1] < in->id_offsets[m]) return fail(KP_E_INVAL, "id_offsets decrease at message %u", m);
+    if (in->id_offsets[in->n_messages] != in->n_ids)
+      return fail(KP_E_INVAL, "id_offsets end at %u of %u ids", in->id_offsets[in->n_messages], in->n_ids);
+  } else if (in->n_ids) {
+    return fail(KP_E_INVAL, "id_offsets end at 0 of %u ids", in->n_ids);
+  }
+  for (uint32_t j = 0; j < in->n_ids; j++) {
+    if (!in->ids[j]) return fail(KP_E_INVAL, "id %u is null", j);
+    if (strnlen(in->ids[j], IR_KEY_BYTES) >= IR_KEY_BYTES)
+      return fail(KP_E_UNSUPPORTED, "id %u is longer than %d bytes", j, IR_KEY_BYTES - 1);
+  }
+  uint32_t with_id = 0;
+  for (uint32_t i = 0; i < in->n_nodes; i++) {
+    if (!in->node_ids[i]) continue;
+    if (strnlen(in->node_ids[i], IR_KEY_BYTES) >= IR_KEY_BYTES)
+      return fail(KP_E_UNSUPPORTED, "node %u: an instance id longer than %d bytes", i, IR_KEY_BYTES - 1);
+    with_id++;
+  }
+  if (in->table_log2 && (1ull << in->table_log2) <= with_id)
+    return fail(KP_E_INVAL, "a forced table of %llu slots for %u nodes with an id", 1ull << in->table_log2, with_id);
+  if (n_with_id) *n_with_id = with_id;
+  return KP_OK;
+}
+
+static int32_t InterruptBuild(kp_cluster_plan* plan) {
+  kp_ctx* ctx = plan->ctx;
+  const kp_cluster& cl = plan->cluster()->cl;
+  const uint32_t N = cl.n_nodes;
+  auto is = std::make_shared<InterruptState>();
+  std::map<std::pair<string, string>, uint32_t> pairs;
+  vector<uint32_t> node_pair(std::max<uint32_t>(N, 1), IR_NONE);
+  vector<uint8_t> deleting(std::max<uint32_t>(N, 1), 0);
+  for (uint32_t i = 0; i < N; i++) {
+    const kp_existing_node& n = cl.nodes[i].node;
+    if (n.n_labels && !n.labels) return fail(KP_E_INVAL, "node %u: null labels", i);
+    const char *type = nullptr, *zone = nullptr;
+    for (uint32_t j = 0; j < n.n_labels; j++) {
+      if (!n.labels[j].key) return fail(KP_E_INVAL, "node %u: null label key", i);
+      if (!strcmp(n.labels[j].key, "node.kubernetes.io/instance-type")) type = n.labels[j].value;
+      else if (!strcmp(n.labels[j].key, "topology.kubernetes.io/zone")) zone = n.labels[j].value;
+    }
+    if (type && zone && *type && *zone)
+      node_pair[i] = pairs.emplace(std::make_pair(string(type), string(zone)), (uint32_t)pairs.size()).first->second;
+    deleting[i] = cl.nodes[i].deleting ? 1 : 0;
+  }
+  Blob blob;
+  const size_t o_pair = blob.put(node_pair), o_del = blob.put(deleting);
+  HIPCHK(is->buf.alloc(blob.total()));
+  uint8_t* base = (uint8_t*)is->buf.p;
+  HIPCHK(hipMemcpyAsync(base, blob.host.data(), blob.host.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  is->a.node_pair = (const uint32_t*)(base + o_pair), is->a.node_deleting = base + o_del;
+  is->a.n_pairs = (int)pairs.size(), is->a.n_nodes = (int)N;
+  plan->interrupt = std::move(is);
+  return KP_OK;
+}
+
+extern "C" {
+
+int32_t kp_interruptions_validate(const kp_interrupt_in* in) { return InterruptCheck(in, nullptr); }
+
+int32_t kp_cluster_interruptions(kp_cluster_plan* plan, const kp_interrupt_in* in, kp_interrupt_node* out_nodes,
+                                 uint32_t* out_matches, kp_interrupt_delete* deletes, uint32_t* n_deletes,
+                                 kp_interrupt_mark* marks, uint32_t* n_marks, uint64_t* counts, kp_solve_stats* stats) {
+  if (n_deletes) *n_deletes = 0;
+  if (n_marks) *n_marks = 0;
+  if (!plan || !in || !n_deletes || !n_marks) return fail(KP_E_INVAL, "null argument");
+  kp_ctx* ctx = plan->ctx;
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  HIPCHK(hipSetDevice(ctx->device));
+  if (stats) memset(stats, 0, sizeof *stats);
+  const auto t0 = std::chrono::steady_clock::now();
+  const OwnedCluster* oc = plan->cluster();
+  if (!oc) return fail(KP_E_INVAL, "the plan holds no cluster");
+  if (plan->general) {
+    if (int32_t rc = CatalogsAlive(oc->alive)) return rc;
+  } else {  // a plan of the batched simulation kernel: kp_cluster_simulate's stale-plan refusal
+    if (int32_t rc = CatalogsAlive(plan->cp->B->alive)) return rc;
+    if (SeqnumsOf(plan->cp->B->catalogs) != plan->cp->B->seqnums)
+      return fail(KP_E_INVAL, "stale plan: a catalogue's seqnum changed since it was prepared (kp_cluster_refresh)");
+  }
+  if (in->n_nodes != oc->cl.n_nodes)
+    return fail(KP_E_INVAL, "interruptions for %u nodes; the plan's snapshot has %u", in->n_nodes, oc->cl.n_nodes);
+  uint32_t with_id = 0;
+  if (int32_t rc = InterruptCheck(in, &with_id)) return rc;
+  if (!plan->interrupt)
+    if (int32_t rc = InterruptBuild(plan)) return rc;
+  InterruptState& is = *plan->interrupt;
+  const uint32_t N = in->n_nodes, M = in->n_messages, E = in->n_ids;
+  if (!in->table_log2 && with_id >= (1u << 30)) return fail(KP_E_UNSUPPORTED, "%u nodes with an id", with_id);
+  uint32_t slots = 2;  // chosen: the least power of two that leaves the table at most half full
+  if (in->table_log2) slots = 1u << in->table_log2;
+  else
+    while (slots < 2 * (with_id + 1)) slots <<= 1;
+  // strings to 32-byte slots
+  vector<uint8_t> node_key((size_t)std::max<uint32_t>(N, 1) * IR_KEY_BYTES, 0), has_id(std::max<uint32_t>(N, 1), 0);
+  for (uint32_t i = 0; i < N; i++) {
+    if (!in->node_ids[i]) continue;
+    has_id[i] = 1;
+    memcpy(&node_key[(size_t)i * IR_KEY_BYTES], in->node_ids[i], strlen(in->node_ids[i]));
+  }
+  vector<uint8_t> entry_key((size_t)std::max<uint32_t>(E, 1) * IR_KEY_BYTES, 0), kind(std::max<uint32_t>(M, 1), 0);
+  vector<uint32_t> entry_msg(std::max<uint32_t>(E, 1), 0);
+  for (uint32_t m = 0; m < M; m++) {
+    kind[m] = (uint8_t)in->kinds[m];
+    for (uint32_t j = in->id_offsets[m]; j < in->id_offsets[m + 1]; j++) {
+      entry_msg[j] = m;
+      memcpy(&entry_key[(size_t)j * IR_KEY_BYTES], in->ids[j], strlen(in->ids[j]));
+    }
+  }
+  InterruptArgs a = is.a;
+  const size_t P = (size_t)std::max(a.n_pairs, 1), N1 = std::max<uint32_t>(N, 1), E1 = std::max<uint32_t>(E, 1);
+  const size_t nb = (size_t)std::max(interrupt_blocks((int)N), 1);
+  Blob blob;
+  const size_t o_nkey = blob.put(node_key), o_has = blob.put(has_id), o_ekey = blob.put(entry_key),
+               o_emsg = blob.put(entry_msg), o_kind = blob.put(kind);
+  // the regions one fill sets to all-ones words, then those one fill zeroes: each group contiguous
+  const size_t o_table = blob.reserve_dev(4 * ((size_t)slots + N1 + P));
+  const size_t o_zero = blob.reserve_dev(4 * (N1 + N1 + P));
+  const size_t o_sums = blob.reserve_dev(4 * IR_SUMS * nb), o_tot = blob.reserve_dev(4 * IR_SUMS),
+               o_nodes = blob.reserve_dev(sizeof(IrNodeOut) * N1), o_match = blob.reserve_dev(4 * E1),
+               o_del = blob.reserve_dev(sizeof(IrDelete) * N1), o_mark = blob.reserve_dev(sizeof(IrMark) * N1);
+  if (blob.total() > is.call_bytes) {
+    HIPCHK(is.call.alloc(blob.total()));
+    is.call_bytes = blob.total();
+  }
+  uint8_t* base = (uint8_t*)is.call.p;
+  a.node_key = (const IrKey*)(base + o_nkey), a.node_has_id = base + o_has;
+  a.entry_key = (const IrKey*)(base + o_ekey), a.entry_msg = (const uint32_t*)(base + o_emsg), a.msg_kind = base + o_kind;
+  a.n_nodes = (int)N, a.n_entries = (int)E, a.table_mask = slots - 1;
+  a.table = (uint32_t*)(base + o_table), a.node_first = a.table + slots, a.pair_first = a.node_first + N1;
+  a.node_kinds = (uint32_t*)(base + o_zero), a.node_count = a.node_kinds + N1, a.pair_count = a.node_count + N1;
+  a.block_sums = (uint32_t*)(base + o_sums), a.totals = (uint32_t*)(base + o_tot);
+  a.out_nodes = (IrNodeOut*)(base + o_nodes), a.out_matches = (uint32_t*)(base + o_match);
+  a.deletes = (IrDelete*)(base + o_del), a.marks = (IrMark*)(base + o_mark);
+  hipStream_t st = ctx->stream;
+  HIPCHK(hipMemcpyAsync(base, blob.host.data(), blob.host.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(hipEventRecord(ctx->ev0, st));
+  HIPCHK(hipMemsetAsync(base + o_table, 0xFF, 4 * ((size_t)slots + N1 + P), st));
+  HIPCHK(hipMemsetAsync(base + o_zero, 0, 4 * (N1 + N1 + P), st));
+  HIPCHK(launch_interruptions(a, st));
+  HIPCHK(hipEventRecord(ctx->ev1, st));
+  uint32_t tot[IR_SUMS] = {};
+  HIPCHK(hipMemcpyAsync(tot, a.totals, sizeof tot, hipMemcpyDeviceToHost, st));
+  if (out_nodes && N) HIPCHK(hipMemcpyAsync(out_nodes, a.out_nodes, sizeof(IrNodeOut) * N, hipMemcpyDeviceToHost, st));
+  if (out_matches && E) HIPCHK(hipMemcpyAsync(out_matches, a.out_matches, 4 * (size_t)E, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (tot[0] > N || tot[1] > N) return fail(KP_E_DEVICE, "the device counted %u deletes, %u marks over %u nodes", tot[0], tot[1], N);
+  // the two lists are as long as the device counted them
+  if (deletes && tot[0]) HIPCHK(hipMemcpyAsync(deletes, a.deletes, sizeof(IrDelete) * tot[0], hipMemcpyDeviceToHost, st));
+  if (marks && tot[1]) HIPCHK(hipMemcpyAsync(marks, a.marks, sizeof(IrMark) * tot[1], hipMemcpyDeviceToHost, st));
+  if ((deletes && tot[0]) || (marks && tot[1])) HIPCHK(hipStreamSynchronize(st));
+  *n_deletes = tot[0], *n_marks = tot[1];
+  if (counts) {
+    for (int k = 0; k < KP_MESSAGE_KIND_COUNT; k++) counts[k] = 0;
+    for (int k = KP_MSG_SCHEDULED_CHANGE; k <= KP_MSG_INSTANCE_TERMINATED; k++) counts[k] = tot[k];
+  }
   if (stats) {
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));

@@ -149,6 +149,10 @@ def load_lib(path=None):
                                               P(abi.SolveStats)]),
         "kp_cluster_detect_drift": (C.c_int32, [C.c_void_p, P(abi.DriftIn), C.c_void_p, P(C.c_uint64),
                                                 P(abi.SolveStats)]),
+        "kp_interruptions_validate": (C.c_int32, [P(abi.InterruptIn)]),
+        "kp_cluster_interruptions": (C.c_int32, [C.c_void_p, P(abi.InterruptIn), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 P(C.c_uint32), C.c_void_p, P(C.c_uint32), P(C.c_uint64),
+                                                 P(abi.SolveStats)]),
         "kp_cluster_simulate_explained": (C.c_int32, [C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32), C.c_uint32,
                                                       C.c_int32, P(C.c_uint32), C.c_uint32, P(abi.SimResult),
                                                       P(abi.SimWhy), P(C.c_uint64), P(C.c_uint64), P(abi.SolveStats)]),
@@ -1115,6 +1119,32 @@ class ClusterPlan:
         _check(self.ctx.lib, self.ctx.lib.kp_cluster_detect_drift(self.h, C.byref(di), out.ctypes.data if records else None,
                                                                   counts, C.byref(st)))
         return (out[:n] if records else None), [int(c) for c in counts], stats_dict(st)
+
+    def interruptions(self, messages, node_ids, table_log2=0, raw=False):
+        """kp_cluster_interruptions: messages [(kind abi.MSG_*, [instance id])] resolved against the snapshot's nodes,
+        whose instance ids are node_ids (None: no provider id). Returns a dict: nodes [{first_message, kinds,
+        n_messages, flags}] per node, matches [nodes matched] per (message, id) entry, deletes [{node, message, kind}]
+        in node order, marks [{node, n_nodes}] in order of node, counts (deletes per kind) and stats. raw=True leaves
+        nodes, matches, deletes and marks as the numpy arrays the call wrote. table_log2 forces the join's table size."""
+        arena = Arena()
+        ii = abi.build_interrupt_in(arena, messages, node_ids, table_log2)
+        n, e = len(node_ids), int(ii.n_ids)
+        nodes = np.zeros(max(n, 1), dtype=abi.interrupt_node_dtype())
+        matches = np.zeros(max(e, 1), dtype=np.uint32)
+        deletes = np.zeros(max(n, 1), dtype=abi.interrupt_delete_dtype())
+        marks = np.zeros(max(n, 1), dtype=abi.interrupt_mark_dtype())
+        nd, nm = C.c_uint32(0), C.c_uint32(0)
+        counts, st = (C.c_uint64 * abi.MESSAGE_KIND_COUNT)(), abi.SolveStats()
+        _check(self.ctx.lib, self.ctx.lib.kp_cluster_interruptions(self.h, C.byref(ii), nodes.ctypes.data,
+                                                                   matches.ctypes.data, deletes.ctypes.data, C.byref(nd),
+                                                                   marks.ctypes.data, C.byref(nm), counts, C.byref(st)))
+        out = {"nodes": nodes[:n], "matches": matches[:e], "deletes": deletes[:nd.value], "marks": marks[:nm.value],
+               "counts": [int(c) for c in counts], "stats": stats_dict(st)}
+        if not raw:
+            for key in ("nodes", "deletes", "marks"):
+                out[key] = [{f: int(r[f]) for f in r.dtype.names if f != "reserved"} for r in out[key]]
+            out["matches"] = [int(x) for x in out["matches"]]
+        return out
 
     def close(self):
         if self.h:

@@ -702,6 +702,67 @@ def launch_templates_dict(base, lt, type_config, configs, ovr, zones, amis, inst
     return out
 
 
+# enum kp_message_kind; KP_INTERRUPT_*
+MSG_NO_OP, MSG_REBALANCE_RECOMMENDATION, MSG_SCHEDULED_CHANGE, MSG_SPOT_INTERRUPTED, MSG_INSTANCE_STOPPED, \
+    MSG_INSTANCE_TERMINATED = range(6)
+MESSAGE_KIND_NAMES = ("no_op", "rebalance_recommendation", "scheduled_change", "spot_interrupted", "instance_stopped",
+                      "instance_terminated")
+MESSAGE_KIND_COUNT = 6
+INTERRUPT_DELETE, INTERRUPT_ALREADY_DELETING, INTERRUPT_ICE = 1, 2, 4
+
+
+class InterruptNode(C.Structure):
+    _fields_ = [("first_message", C.c_int32), ("kinds", C.c_uint32), ("n_messages", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class InterruptDelete(C.Structure):
+    _fields_ = [("node", C.c_uint32), ("message", C.c_uint32), ("kind", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class InterruptMark(C.Structure):
+    _fields_ = [("node", C.c_uint32), ("n_nodes", C.c_uint32)]
+
+
+class InterruptIn(C.Structure):
+    _fields_ = [("kinds", C.POINTER(C.c_int32)), ("id_offsets", C.POINTER(C.c_uint32)), ("ids", C.POINTER(C.c_char_p)),
+                ("node_ids", C.POINTER(C.c_char_p)), ("n_messages", C.c_uint32), ("n_ids", C.c_uint32),
+                ("n_nodes", C.c_uint32), ("table_log2", C.c_uint32)]
+
+
+def interrupt_node_dtype():
+    """kp_interrupt_node"""
+    import numpy as np
+    return np.dtype([("first_message", "<i4"), ("kinds", "<u4"), ("n_messages", "<u4"), ("flags", "<u4")])
+
+
+def interrupt_delete_dtype():
+    """kp_interrupt_delete"""
+    import numpy as np
+    return np.dtype([("node", "<u4"), ("message", "<u4"), ("kind", "<i4"), ("reserved", "<u4")])
+
+
+def interrupt_mark_dtype():
+    """kp_interrupt_mark"""
+    import numpy as np
+    return np.dtype([("node", "<u4"), ("n_nodes", "<u4")])
+
+
+def build_interrupt_in(arena, messages, node_ids, table_log2=0):
+    """messages [(kind, [instance id])], node_ids [instance id or None per node] -> kp_interrupt_in (buffers kept by
+    the arena)."""
+    kinds = arena.arr(C.c_int32, [int(k) for k, _ in messages])
+    offs, flat = [0], []
+    for _, ids in messages:
+        flat.extend(ids)
+        offs.append(len(flat))
+    ii = InterruptIn(kinds if messages else None, arena.arr(C.c_uint32, offs),
+                     arena.arr(C.c_char_p, [arena.s(x) for x in flat]) if flat else None,
+                     arena.arr(C.c_char_p, [arena.s(x) for x in node_ids]) if node_ids else None,
+                     len(messages), len(flat), len(node_ids), int(table_log2))
+    arena.keep.append(ii)
+    return ii
+
+
 # ------------------------------------------------------------------------------------------------
 # Marshalling: Python model objects (kpamd.model) -> ctypes, keeping every buffer alive on `self.keep`.
 # ------------------------------------------------------------------------------------------------

@@ -139,6 +139,7 @@ class ClusterNode:
     pods: List[int] = field(default_factory=list)   # indices into Cluster.pod_*
     deleting: bool = False                           # MarkedForDeletion: its pods join every simulation
     drifted: Optional[float] = None                  # transition time of its Drifted condition (None: not drifted)
+    provider_id: Optional[str] = None                # the NodeClaim's status.providerID (kpamd.interruption reads it)
 
 
 @dataclass
